@@ -31,6 +31,14 @@ partition): no data-path collective, except the repartition leg's all-to-all.  E
 runs barrier + synchronize around exactly --steps timed steps; value = all ranks' records /
 max-over-ranks time.
 
+A plain run sets up, warms up, times --steps steps and prints the line.  `--full` adds what takes
+runs of its own: `cpu_baseline`, the PCIe-inclusive and pull-query side numbers, the stream-copy
+and random-gather ceilings (null in a plain line).  `--dump-outputs DIR` writes, after the timed
+steps, what the last step computed as DIR/<name>.npy (float64; byte and flag arrays float32; at
+most 64 MB): the step's statistics and row count, and the rows it materialized for a fixed sample
+of the keys, sorted by (key, window start) (the other legs: a fixed sample of their output
+arrays).  The inputs are seeded: the same arguments give the same files.
+
 Output: one JSON line (rank 0) with `roofline` and `cpu_baseline`:
   roofline.achieved / frac   algorithmic bytes per step ÷ the wall time of one
                              step (ms_per_step, barrier-to-barrier) — the conservative figure;
@@ -82,8 +90,13 @@ def parse():
     ap.add_argument("--sparse-keys", action="store_true",
                     help="possible_fraud: card numbers spread over [0, 2^53) by a bijection of the dense ids "
                          "(the key range does not fit 32 bits)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline, the PCIe-inclusive and "
+                         "pull-query side numbers, the stream-copy and random-gather ceilings")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="target CPU baseline sample time per run")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--traffic-json", default=os.path.join(REPO, "profiles", "traffic.json"))
     ap.add_argument("--engine", choices=["part", "atomic"], default="part")
     ap.add_argument("--unpack", action="store_true",
@@ -93,13 +106,17 @@ def parse():
     ap.add_argument("--sparse-ids", action="store_true",
                     help="clickstream_join: user ids spread over 2^40 (a bijection of 1..U), so the dense "
                          "direct-map index is ineligible and the hash-probe kernel runs")
-    ap.add_argument("--no-extras", action="store_true", help="skip the PCIe-inclusive and pull-query side numbers")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the PCIe-inclusive and pull-query side numbers")
     ap.add_argument("--exchange", choices=["rccl", "gloo"], default="rccl",
                     help="repartition_sum at N > 1: RCCL all-to-all over xGMI (production), or the same two "
                          "collective steps over a gloo process group through host memory (rehearsal)")
     ap.add_argument("--one-device", action="store_true",
                     help="every rank on cuda:0 (with --exchange gloo: an N-rank rehearsal on a 1-GPU box)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu_baseline = args.no_extras = True
+    return args
 
 
 # ------------------------------------------------------------------ multi-GPU launch
@@ -231,6 +248,82 @@ def line(metric, value, world, args, ms_step, dtype, data, config, roof, cpu, **
     print(json.dumps(out), flush=True)
 
 
+# ------------------------------------------------------------------ --dump-outputs
+
+DUMP_LIMIT = 60 << 20  # array bytes over all files of one run (64 MB with room for the .npy headers)
+DUMP_KEYS = 1 << 14    # keys of a large materialized table that are pulled and written
+
+
+def _sample(a, k):
+    """`a` (numpy array or torch tensor) whole when it has at most k elements, otherwise its
+    elements at k positions drawn with a seed fixed by its length (the same positions in every
+    array of that length, so the columns of one table stay aligned), as a numpy array."""
+    n = len(a)
+    if isinstance(a, np.ndarray):
+        return a[np.sort(np.random.default_rng(n).integers(0, n, k))] if n > k else a
+    import torch
+    if n > k:
+        a = a[torch.from_numpy(np.sort(np.random.default_rng(n).integers(0, n, k))).to(a.device)]
+    return a.cpu().numpy()
+
+
+def dump_outputs(args, rank, arrays):
+    """Rank 0 writes {name: array} as DIR/<name>.npy: float64 (every integer here — counts, sums,
+    keys, timestamps — is below 2^53, so exact), one-byte elements (bytes, flags) as float32; an
+    array too large for its share of DUMP_LIMIT is sampled (_sample)."""
+    if not args.dump_outputs or rank != 0:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    k = DUMP_LIMIT // (8 * max(len(arrays), 1))  # elements per file: one k, so equal lengths stay aligned
+    for name, a in arrays.items():
+        if not hasattr(a, "dtype"):
+            a = np.asarray(a)
+        small = (a.itemsize if isinstance(a, np.ndarray) else a.element_size()) == 1
+        a = _sample(a, k)
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a.astype(np.float32 if small else np.float64))
+
+
+def bits_at(bitmap, idx):
+    """Bits `idx` (a device index tensor) of an LSB-first device bitmap, as a uint8 device tensor."""
+    return (bitmap[idx >> 3] >> (idx & 7).to(bitmap.dtype)) & 1
+
+
+def table_arrays(rows, prefix="table_"):
+    """The columns of a materialized result (AggHandle.get / snapshot, sorted by (key, ws))."""
+    out = {"rows": [rows["n"]], "ws": rows["ws"], "we": rows["we"], "rowtime": rows["rowtime"]}
+    if isinstance(rows.get("key"), np.ndarray):
+        out["key"] = rows["key"]
+    for i, (v, nul) in enumerate(zip(rows["values"], rows["nulls"])):
+        out["value%d" % i] = np.where(nul, 0, v)
+        out["null%d" % i] = nul
+    return {prefix + k: v for k, v in out.items()}
+
+
+def decoded_arrays(cols):
+    """SerdeHandle.columns' host copy of a decoded batch (the legs' records all decode: every
+    value is defined)."""
+    out = {"key_valid": cols["key_valid"], "row_valid": cols["row_valid"]}
+    if "key" in cols:
+        out["key"] = cols["key"]
+    for i, (v, ok) in enumerate(zip(cols["cols"], cols["valid"])):
+        out["col%d" % i], out["col%d_valid" % i] = v, ok
+    return out
+
+
+def sample_keys(keys, k=DUMP_KEYS):
+    """A fixed sample of the distinct values of a device key column, sorted, on the host."""
+    return np.unique(_sample(keys, k))
+
+
+STATS_FIELDS = ("rows_in", "rows_accepted", "dropped_null_key", "dropped_null_row", "dropped_bad_ts",
+                "windows_applied", "windows_late", "stream_time")
+
+
+def stats_array(st):
+    """A push's khip_batch_stats (or the sum over a step's pushes) in STATS_FIELDS order."""
+    return [st.get(k, 0) for k in STATS_FIELDS]
+
+
 def push_phases(kt, launches):
     launches = max(launches, 1)
     return {k: kt[k] / launches for k in ("stream_time_ms", "dict_ms", "partition_ms", "apply_ms", "finalize_ms")}
@@ -320,14 +413,18 @@ def bench_serde_json(args, lib, rank, world, local):
     sd = abi.SerdeHandle(lib, "JSON", [("AMOUNT", "INT64", 0)], key_type="INT64", key_format="KAFKA", device=local)
     torch.cuda.synchronize()
 
+    last = {}
+
     def step():
-        d, nerr = sd.decode_device(ts, koff, kb, voff, vb)
+        last["decoded"], nerr = sd.decode_device(ts, koff, kb, voff, vb)
         return nerr
 
     for _ in range(max(args.warmup, 1)):
         nerr = step()
     assert nerr == 0, nerr
     nerr, elapsed = timed_loop(step, args.steps, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args, rank, {"errors": [nerr], **decoded_arrays(sd.columns(last["decoded"], ["INT64"]))})
     sd.close()
     if rank != 0:
         return
@@ -378,14 +475,18 @@ def bench_serde_avro(args, lib, rank, world, local):
                          avro_schema=[("AMOUNT", "long", 0)], avro_schema_id=1)
     torch.cuda.synchronize()
 
+    last = {}
+
     def step():
-        d, nerr = sd.decode_device(ts, koff, kb, voff, vb)
+        last["decoded"], nerr = sd.decode_device(ts, koff, kb, voff, vb)
         return nerr
 
     for _ in range(max(args.warmup, 1)):
         nerr = step()
     assert nerr == 0, nerr
     nerr, elapsed = timed_loop(step, args.steps, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args, rank, {"errors": [nerr], **decoded_arrays(sd.columns(last["decoded"], ["INT64"]))})
     sd.close()
     if rank != 0:
         return
@@ -467,6 +568,9 @@ def bench_sink_json(args, lib, rank, world, local):
         kl, vl = step()
     assert kl == 16 * n, kl
     (kl, vl), elapsed = timed_loop(step, args.steps, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args, rank, {"key_len": [kl], "value_len": [vl], "key_offsets": koff, "value_offsets": voff,
+                                  "key_bytes": kbytes[:kl], "value_bytes": vbytes[:vl], "value_null": vnull})
     s.close()
     if rank != 0:
         return
@@ -540,6 +644,8 @@ def bench_table_agg(args, lib, rank, world, local):
         acc = step()
     acc, elapsed = timed_loop(step, args.steps, world)
     groups = h.count_rows(None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args, rank, {"rows_accepted": [acc], "count_rows": [groups], **table_arrays(h.get())})
     h.close()
     if rank != 0:
         return
@@ -592,6 +698,9 @@ def bench_session(args, lib, rank, world, local):
     assert st["rows_accepted"] == n, st
     st, elapsed = timed_loop(step, args.steps, world)
     groups = h.count_rows(None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args, rank, {"stats": stats_array(st), "count_rows": [groups],
+                                  **table_arrays(h.get(sample_keys(card)))})
     h.close()
     if rank != 0:
         return
@@ -696,6 +805,15 @@ def bench_possible_fraud(args, lib, rank, world, local):
     (st, rows), elapsed = timed_loop(step, args.steps, world)
     kt = h.kernel_times()
     groups = int(h.snapshot_size())  # host bookkeeping: no device work after the timed loop
+    if args.dump_outputs and rank == 0:
+        # the step's results, and the rows it materialized for a fixed sample of the card numbers
+        qk = sample_keys(card)
+        if args.utf8:
+            kb = synth.card_utf8(qk)[1].reshape(-1, 16)
+            if args.card_format == "alnum":
+                kb[:, 0] = ord("C")
+            qk = [bytes(k) for k in kb]
+        dump_outputs(args, rank, {"stats": stats_array(st), "having_rows": [rows], **table_arrays(h.get(qk))})
 
     pcie = pull = None
     if rank == 0 and not args.no_extras and not args.utf8 and n <= 100_000_000:
@@ -826,6 +944,8 @@ def bench_hourly_metrics(args, lib, rank, world, local):
     h.kernel_times(reset=True)
     (st, groups), elapsed = timed_loop(step, args.steps, world)
     kt = h.kernel_times()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args, rank, {"stats": stats_array(st), "count_rows": [groups], **table_arrays(h.get())})
     h.close()
     if rank != 0:
         return
@@ -915,6 +1035,9 @@ def bench_hopping_double(args, lib, rank, world, local):
     h.kernel_times(reset=True)
     (st, groups), elapsed = timed_loop(step, args.steps, world)
     kt = h.kernel_times()
+    if args.dump_outputs and rank == 0:  # SUM / AVG are added in LDS-atomic order: equal within DESIGN's bound
+        dump_outputs(args, rank, {"stats": stats_array(st), "count_rows": [groups],
+                                  **table_arrays(h.get(sample_keys(key, 1 << 10)))})
     h.close()
     if rank != 0:
         return
@@ -948,7 +1071,7 @@ def bench_hopping_double(args, lib, rank, world, local):
                            "survey_equivalent_frac": BYTES_PER_RECORD_C3 * n / (ms_step / 1000.0) / 1e9 / HBM_PEAK_GBS,
                            "phase_ms_per_step": phase,
                            "per_kernel": per_phase_block(phase, value_phase_bytes(False), n),
-                           "stream_copy_GBps": stream_copy_gbs()})
+                           "stream_copy_GBps": stream_copy_gbs() if args.full else None})
     cpu = None
     if world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_agg(lambda m: synth.hopping_double(0, m, n), False,
@@ -1034,6 +1157,14 @@ def bench_join(args, lib, rank, world, local):
     for _ in range(max(args.warmup, 1)):
         rows = step()
     rows, elapsed = timed_loop(step, args.steps, world)
+    if args.dump_outputs and rank == 0:
+        # a fixed sample of the stream rows: emitted, matched (of the emitted), the right column and
+        # its null flag (of the matched); what the probe leaves unspecified is written as 0
+        idx = torch.from_numpy(np.sort(np.random.default_rng(n).integers(0, n, min(n, 1 << 20)))).to("cuda")
+        e = bits_at(emit, idx)
+        mt = bits_at(matched, idx) & e
+        dump_outputs(args, rank, {"emitted_rows": [rows], "sample_row": idx, "emit": e, "matched": mt,
+                                  "level": col[idx] * mt, "level_null": bits_at(null, idx) & mt})
     # khip_table_create: cap = next_pow2(2 x hint) slots of 16 bytes (one INT column: the compact
     # layout, the value inside the meta word); a probe's first read is its 32-byte home pair
     info = {"table_bytes": (1 << max(10, (2 * U - 1).bit_length())) * 16, "slot_bytes": 16, "home_read_bytes": 32}
@@ -1043,8 +1174,9 @@ def bench_join(args, lib, rank, world, local):
     ms_step = elapsed * 1000.0 / args.steps
     roof = roofline(BYTES_PER_PROBE_C4 * n, ms_step, None, None, load_traffic(args.traffic_json, "clickstream_join" + ("_sparse_ids" if args.sparse_ids else ""), n),
                     BYTES_PER_PROBE_C4, kernel="khip_table_probe_device (probe kernels) + emitted count",
-                    extra={"stream_copy_GBps": stream_copy_gbs(), "table": info,
-                           "random_gather_rows_per_s": random_gather_rows_per_s(info["table_bytes"])})
+                    extra={"stream_copy_GBps": stream_copy_gbs() if args.full else None, "table": info,
+                           "random_gather_rows_per_s": random_gather_rows_per_s(info["table_bytes"]) if args.full
+                           else None})
     cpu = None
     if world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_join(U, args.cpu_seconds, args.sparse_ids)
@@ -1171,6 +1303,9 @@ def bench_repartition(args, lib, rank, world, local):
     state["timed"] = True
     (st, rows, m), elapsed = timed_loop(step, args.steps, world)
     kt = h.kernel_times()
+    if args.dump_outputs and rank == 0:  # rank 0's share of the regions
+        dump_outputs(args, rank, {"stats": stats_array(st), "count_rows": [rows], "rows_received": [m],
+                                  **table_arrays(h.get(sample_keys(region, 1 << 12)))})
     h.close()
     rp.close()
     if comm is not None:

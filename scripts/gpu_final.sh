@@ -20,7 +20,7 @@ tests)
   [ $rc -gt 1 ] && exit $rc
   timeout -k 10 300 python -u __graft_entry__.py smoke > $D/smoke.log 2>&1 || { echo smoke failed; tail $D/smoke.log; exit 3; }
   tail -2 $D/smoke.log
-  timeout -k 10 400 python -u bench.py > $D/bench.jsonl 2> $D/bench.err || { echo "bench failed"; tail -20 $D/bench.err; exit 4; }
+  timeout -k 10 400 python -u bench.py --full > $D/bench.jsonl 2> $D/bench.err || { echo "bench failed"; tail -20 $D/bench.err; exit 4; }
   cut -c1-400 $D/bench.jsonl
   STEPS=3 bash scripts/profile_leg.sh $ITAG possible_fraud || exit 6
   ;;
@@ -28,7 +28,7 @@ legs)
   for LA in ${LEGS:-$ALL_LEGS}; do
     L=${LA%%:*}; X=""; [ "$LA" != "$L" ] && X=$(echo "${LA#*:}" | tr ':' ' ')
     T=$L$(echo "$X" | tr -c 'a-z0-9' '_' | sed 's/_*$//')
-    timeout -k 10 400 python -u bench.py --config $L $X > $D/leg_$T.jsonl 2> $D/leg_$T.err || { echo "leg $LA failed"; tail -20 $D/leg_$T.err; exit 5; }
+    timeout -k 10 400 python -u bench.py --full --config $L $X > $D/leg_$T.jsonl 2> $D/leg_$T.err || { echo "leg $LA failed"; tail -20 $D/leg_$T.err; exit 5; }
     cut -c1-250 $D/leg_$T.jsonl
   done
   ;;

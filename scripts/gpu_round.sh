@@ -22,11 +22,11 @@ if [ "${SUITE:-1}" = 1 ]; then
   grep -E "^FAILED" $D/suite.log | head -20
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 400 python3 bench.py ${BENCH_ARGS:-} > $D/bench.jsonl 2> $D/bench.err || { echo "bench failed"; tail -20 $D/bench.err; exit 4; }
+  timeout -k 10 400 python3 bench.py --full ${BENCH_ARGS:-} > $D/bench.jsonl 2> $D/bench.err || { echo "bench failed"; tail -20 $D/bench.err; exit 4; }
   cut -c1-600 $D/bench.jsonl
 fi
 for L in ${LEGS:-}; do
-  timeout -k 10 400 python3 bench.py --config $L ${LEG_ARGS:-} > $D/leg_$L.jsonl 2> $D/leg_$L.err || { echo "leg $L failed"; tail -20 $D/leg_$L.err; exit 5; }
+  timeout -k 10 400 python3 bench.py --full --config $L ${LEG_ARGS:-} > $D/leg_$L.jsonl 2> $D/leg_$L.err || { echo "leg $L failed"; tail -20 $D/leg_$L.err; exit 5; }
   cut -c1-400 $D/leg_$L.jsonl
 done
 if [ "${PROF:-1}" = 1 ]; then

@@ -47,6 +47,46 @@ def test_single_gpu_does_not_relaunch(monkeypatch):
         bench.main()
 
 
+# ---- a plain run times the steps only; --full adds the measurements that take runs of their own ----
+
+def test_plain_run_skips_side_measurements(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and a.no_cpu_baseline and a.no_extras and a.dump_outputs is None and a.steps == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and not a.no_cpu_baseline and not a.no_extras
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
+    a = bench.parse()
+    assert a.no_cpu_baseline and not a.no_extras
+
+
+def test_dump_outputs_files(tmp_path, monkeypatch):
+    """--dump-outputs: float64 / float32 .npy files within DUMP_LIMIT, a large array as a fixed
+    sample at the same positions in every array of its length, identical from call to call."""
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 1 << 16)
+    n = 100_000
+    big = np.arange(n, dtype=np.int64) * 3
+    arrays = {"stats": [1, 2, 3], "key": big, "count": big + 1, "flag": (big % 2).astype(np.uint8)}
+    out = []
+    for d in ("a", "b"):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--dump-outputs", str(tmp_path / d)])
+        bench.dump_outputs(bench.parse(), 0, arrays)
+        out.append({f: np.load(str(tmp_path / d / f)) for f in sorted(os.listdir(str(tmp_path / d)))})
+    a, b = out
+    assert sorted(a) == ["count.npy", "flag.npy", "key.npy", "stats.npy"]
+    assert sum(v.nbytes for v in a.values()) <= 1 << 16
+    assert all(np.array_equal(a[f], b[f]) for f in a)
+    assert a["stats.npy"].dtype == np.float64 and a["stats.npy"].tolist() == [1.0, 2.0, 3.0]
+    assert a["flag.npy"].dtype == np.float32 and a["key.npy"].dtype == np.float64
+    assert 0 < len(a["key.npy"]) < n and np.array_equal(a["count.npy"], a["key.npy"] + 1)
+    assert np.array_equal(a["flag.npy"], a["key.npy"] % 2) and np.all(np.diff(a["key.npy"]) >= 0)
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    bench.dump_outputs(bench.parse(), 0, arrays)  # no --dump-outputs: nothing is written
+    assert sorted(os.listdir(str(tmp_path))) == ["a", "b"]
+
+
 # ---- profiles/traffic.json: the counter bytes the bench line's roofline.traffic comes from -------
 # Read bytes are measured from request counts by size (tools/pmc_traffic.py, method_version 2).
 # A kernel that streams its input once cannot read less than that input: a figure below it means

@@ -809,6 +809,26 @@ __device__ __forceinline__ int c1_find_id(const KLDS ID* ids, ID id, uint32_t e,
   return -1;
 }
 
+// Closed rows leave a partition for the closed store ONCE per push, on the first pass: every item
+// of that pass moves its closed resident rows, the items that fail included (their retries read
+// the same source region, which keeps the rows until the partition commits).  Later passes only
+// skip closed rows: not counted, no slots, no HAVING count.
+constexpr unsigned long long C1_NOSLOT = ~0ULL;
+constexpr unsigned long long C1_FATAL = 1ULL << 63;  // in `need`: a reservation past the closed store's capacity
+// n slots of the closed store (an item's thread 0).  The host sizes the store for every live row,
+// so a reservation that ends past the capacity is a bug: it gets no slots (nothing is written)
+// and the push fails (fail bit 4, C1_FATAL in need).
+__device__ __forceinline__ unsigned long long c1_reserve_closed(unsigned long long* closed_n, unsigned long long n,
+                                                                unsigned long long cap, uint8_t* failp,
+                                                                unsigned long long* need) {
+  if (!n) return 0ULL;
+  const unsigned long long b = atomicAdd(closed_n, n);
+  if (b + n <= cap) return b;
+  *failp |= 4;
+  atomicOr(need, C1_FATAL);
+  return C1_NOSLOT;
+}
+
 // Work item: p (work == nullptr: item w is partition w) or work[w] = p | sbits << 16 | sub << 20
 // (a retry with 2^sbits sub-passes).  LDS: ids ID[H + 64] | rt u32[H + 64] | ct u32[H + 64] |
 // list u16[H] | segment prefix u32[SEGMAX + 1] | segment bases i32[SEGMAX] (n < 2^31).
@@ -819,7 +839,8 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
     uint64_t* __restrict__ buf0, uint64_t* __restrict__ buf1, const uint8_t* __restrict__ sel,
     const int64_t* __restrict__ cnt, unsigned long long* __restrict__ newcnt, uint8_t* __restrict__ fail,
     unsigned long long* __restrict__ need, int64_t close0, uint64_t* __restrict__ closed,
-    unsigned long long* __restrict__ closed_n, const int64_t* __restrict__ ci, unsigned long long* __restrict__ hnew,
+    unsigned long long* __restrict__ closed_n, unsigned long long closed_cap, const int64_t* __restrict__ ci,
+    unsigned long long* __restrict__ hnew,
     unsigned long long* __restrict__ hclosed, uint32_t* __restrict__ prn, const uint32_t* __restrict__ srecT,
     unsigned long long* __restrict__ dbg) {
   if (ci_ld(ci, CI_GATE) == 0) return;
@@ -1060,6 +1081,53 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
     const uint64_t* src = (isel ? buf1 : buf0) + (uint64_t)p * q.cmax * q.sw;
     // (closed resident rows leave for the closed store in the write-out, phase 4: one pass over the
     // resident rows there, the closed store's slots reserved with the region's)
+    // An item that fails on the first pass moves them here instead (count, reserve, copy), since
+    // its retries skip them.
+    auto evict_failed = [&]() {
+      if (!first || !evict || nrow == 0) return;  // (uniform)
+      auto mine_closed = [&](const uint64_t* row) -> bool {
+        if ((int64_t)row[1] + q.size > close0) return false;
+        if (!sbits) return true;
+        ID id;
+        uint32_t h;
+        row_id(row, &id, &h);
+        return (int)c1_sub(h, sbits) == sub;
+      };
+      int n_cl = 0;
+      for (int64_t r = threadIdx.x; r < nrow; r += NT) n_cl += mine_closed(src + r * q.sw) ? 1 : 0;
+      const int wave_cl = (int)wave_sum(n_cl);
+      if (lane == 0) csum[wave] = wave_cl;
+      lds_barrier();
+      int cl_before = 0, cl_total = 0;
+      for (int k = 0; k < NW; k++) {
+        if (k < wave) cl_before += csum[k];
+        cl_total += csum[k];
+      }
+      if (threadIdx.x == 0)
+        cbase = c1_reserve_closed(closed_n, (unsigned long long)cl_total, closed_cap, &fail[p], need);
+      lds_barrier();
+      const unsigned long long cb = cbase;
+      if (cl_total == 0 || cb == C1_NOSLOT) return;
+      uint64_t ccur = cb + (uint64_t)cl_before;
+      const uint64_t lt = (1ULL << lane) - 1;
+      int nhc = 0;
+      for (int64_t r0 = wave * 64; r0 < nrow; r0 += NT) {
+        const int64_t r = r0 + lane;
+        const uint64_t* row = src + (r < nrow ? r : 0) * q.sw;
+        const bool cl = r < nrow && mine_closed(row);
+        const uint64_t bc = __ballot(cl);
+        if (cl) {
+          uint64_t* cd = closed + (ccur + __popcll(bc & lt)) * q.sw;
+          for (int k = 0; k < q.sw; k++) cd[k] = row[k];
+          nhc += q.hv_active && c1q_having(q, row[3]) ? 1 : 0;
+        }
+        ccur += __popcll(bc);
+      }
+      if (q.hv_active) {
+        nhc = (int)wave_sum(nhc);
+        if (lane == 0 && nhc) atomicAdd(hclosed, (unsigned long long)nhc);
+      }
+    };
     C1M_T(0);
     // 1. records → delta entries, two register sets (chunk c + 1 in flight while c is applied;
     //    chunk 0 was loaded with the item's segments)
@@ -1174,6 +1242,7 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
         rt[e] = 0u;
         ct[e] = 0u;
       }
+      evict_failed();
       lds_barrier();
       if (threadIdx.x == 0) {
         lovf = 0;
@@ -1191,7 +1260,7 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
       const bool has = row_id(row, &id, &h);
       if (sbits && (int)c1_sub(h, sbits) != sub) continue;
       if (evict && (int64_t)row[1] + q.size <= close0) {
-        n_cl++;
+        n_cl += first ? 1 : 0;  // (a later pass: the first one moved it)
         continue;
       }
       if (has) {
@@ -1232,8 +1301,10 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
         lbase = 0;
         newcnt[p] = (unsigned long long)total;
       }
-      // (an item that does not fit its region is retried and reserves nothing here)
-      cbase = cl_total && (int64_t)(lbase + total) <= q.cmax ? atomicAdd(closed_n, (unsigned long long)cl_total) : 0ULL;
+      // (an item that does not fit its region reserves with its own copy, evict_failed)
+      cbase = (int64_t)(lbase + total) <= q.cmax
+                  ? c1_reserve_closed(closed_n, (unsigned long long)cl_total, closed_cap, &fail[p], need)
+                  : 0ULL;
     }
     lds_barrier();
     if ((int64_t)(lbase + total) > q.cmax) {
@@ -1247,6 +1318,7 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
         rt[e] = 0u;
         ct[e] = 0u;
       }
+      evict_failed();
       lds_barrier();
       if (threadIdx.x == 0) nnew = 0;
       lds_barrier();
@@ -1257,6 +1329,7 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
     uint64_t* dst0 = (isel ? buf0 : buf1) + (uint64_t)p * q.cmax * q.sw;
     uint64_t cur = lbase + (uint64_t)wave_before;
     uint64_t ccur = cbase + (uint64_t)cl_before;
+    const bool cmove = first && cbase != C1_NOSLOT;  // closed rows are copied (else only dropped)
     const uint64_t lt = (1ULL << lane) - 1;
     int nh = 0, nhc = 0;
     for (int64_t r0 = wave * 64; r0 < nrow; r0 += NT) {
@@ -1274,7 +1347,7 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
         if (live && has) e = c1_find_id<ID>(ids, id, h >> (32 - log2H), H);
       }
       const uint64_t bc = __ballot(cl);
-      if (cl) {
+      if (cl && cmove) {
         uint64_t* cd = closed + (ccur + __popcll(bc & lt)) * q.sw;
         for (int k = 0; k < q.sw; k++) cd[k] = row[k];
         nhc += q.hv_active && c1q_having(q, row[3]) ? 1 : 0;
@@ -1821,7 +1894,8 @@ __global__ __launch_bounds__(NT, WPE) void k_c1v_merge(
     uint64_t* __restrict__ buf0, uint64_t* __restrict__ buf1, const uint8_t* __restrict__ sel,
     const int64_t* __restrict__ cnt, unsigned long long* __restrict__ newcnt, uint8_t* __restrict__ fail,
     unsigned long long* __restrict__ need, int64_t close0, uint64_t* __restrict__ closed,
-    unsigned long long* __restrict__ closed_n, const int64_t* __restrict__ ci, unsigned long long* __restrict__ hnew,
+    unsigned long long* __restrict__ closed_n, unsigned long long closed_cap, const int64_t* __restrict__ ci,
+    unsigned long long* __restrict__ hnew,
     unsigned long long* __restrict__ hclosed, uint32_t* __restrict__ prn, unsigned long long* __restrict__ dbg) {
   if (ci_ld(ci, CI_GATE) == 0) return;
   if ((ci_ld(ci, CI_ID32) != 0) != (sizeof(ID) == 4)) return;  // the other identity width's
@@ -2061,6 +2135,49 @@ __global__ __launch_bounds__(NT, WPE) void k_c1v_merge(
     const uint64_t* src = (isel ? buf1 : buf0) + (uint64_t)p * q.cmax * q.sw;
     // (closed resident rows leave for the closed store in the write-out, phase 4: one pass over the
     // resident rows there, the closed store's slots reserved with the region's)
+    // An item that fails on the first pass moves them here instead (count, reserve, copy), since
+    // its retries skip them (as k_c1_merge).
+    auto evict_failed = [&]() {
+      if (!first || !evict || nrow == 0) return;  // (uniform)
+      auto mine_closed = [&](const uint64_t* row) -> bool {
+        return (int64_t)row[1] + q.size <= close0 && (!sbits || (int)c1_sub(subh((int64_t)row[0]), sbits) == sub);
+      };
+      int n_cl = 0;
+      for (int64_t r = threadIdx.x; r < nrow; r += NT) n_cl += mine_closed(src + r * q.sw) ? 1 : 0;
+      const int wave_cl = (int)wave_sum(n_cl);
+      if (lane == 0) csum[wave] = wave_cl;
+      lds_barrier();
+      int cl_before = 0, cl_total = 0;
+      for (int k = 0; k < NW; k++) {
+        if (k < wave) cl_before += csum[k];
+        cl_total += csum[k];
+      }
+      if (threadIdx.x == 0)
+        cbase = c1_reserve_closed(closed_n, (unsigned long long)cl_total, closed_cap, &fail[p], need);
+      lds_barrier();
+      const unsigned long long cb = cbase;
+      if (cl_total == 0 || cb == C1_NOSLOT) return;
+      uint64_t ccur = cb + (uint64_t)cl_before;
+      const uint64_t lt = (1ULL << lane) - 1;
+      int nhc = 0;
+      for (int64_t r0 = wave * 64; r0 < nrow; r0 += NT) {
+        const int64_t r = r0 + lane;
+        const uint64_t* row = src + (r < nrow ? r : 0) * q.sw;
+        const bool cl = r < nrow && mine_closed(row);
+        const uint64_t bc = __ballot(cl);
+        if (cl) {
+          uint64_t* cd = closed + (ccur + __popcll(bc & lt)) * q.sw;
+          for (int k = 0; k < q.sw; k++) cd[k] = row[k];
+          nhc += having_ok_words(q.having.a.w_val >= 0 ? row[q.having.a.w_val] : 0,
+                                 q.having.a.w_cnt >= 0 ? row[q.having.a.w_cnt] : 0, q.having) ? 1 : 0;
+        }
+        ccur += __popcll(bc);
+      }
+      if (q.having.active) {
+        nhc = (int)wave_sum(nhc);
+        if (lane == 0 && nhc) atomicAdd(hclosed, (unsigned long long)nhc);
+      }
+    };
     C1M_T(0);
     // 1. records → their pane (window) entries: the AU identities' CASes back to back, then the
     //    collisions probe on together (as k_c1_merge)
@@ -2219,6 +2336,7 @@ __global__ __launch_bounds__(NT, WPE) void k_c1v_merge(
         ids[e] = EMPTY;
         c1v_clear<PM>(q, smem, (int)e);
       }
+      evict_failed();
       lds_barrier();
       if (threadIdx.x == 0) {
         lovf = 0;
@@ -2233,7 +2351,7 @@ __global__ __launch_bounds__(NT, WPE) void k_c1v_merge(
       const uint64_t* row = src + r * q.sw;
       if (sbits && (int)c1_sub(subh((int64_t)row[0]), sbits) != sub) continue;
       if (evict && (int64_t)row[1] + q.size <= close0) {
-        n_cl++;
+        n_cl += first ? 1 : 0;  // (a later pass: the first one moved it)
         continue;
       }
       ID id;
@@ -2275,8 +2393,10 @@ __global__ __launch_bounds__(NT, WPE) void k_c1v_merge(
         lbase = 0;
         newcnt[p] = (unsigned long long)total;
       }
-      // (an item that does not fit its region is retried and reserves nothing here)
-      cbase = cl_total && (int64_t)(lbase + total) <= q.cmax ? atomicAdd(closed_n, (unsigned long long)cl_total) : 0ULL;
+      // (an item that does not fit its region reserves with its own copy, evict_failed)
+      cbase = (int64_t)(lbase + total) <= q.cmax
+                  ? c1_reserve_closed(closed_n, (unsigned long long)cl_total, closed_cap, &fail[p], need)
+                  : 0ULL;
     }
     lds_barrier();
     if ((int64_t)(lbase + total) > q.cmax) {
@@ -2289,6 +2409,7 @@ __global__ __launch_bounds__(NT, WPE) void k_c1v_merge(
         ids[e] = EMPTY;
         c1v_clear<PM>(q, smem, (int)e);
       }
+      evict_failed();
       lds_barrier();
       if (threadIdx.x == 0) nnew = 0;
       lds_barrier();
@@ -2300,6 +2421,7 @@ __global__ __launch_bounds__(NT, WPE) void k_c1v_merge(
     uint64_t* dst0 = (isel ? buf0 : buf1) + (uint64_t)p * q.cmax * q.sw;
     uint64_t cur = lbase + (uint64_t)wave_before;
     uint64_t ccur = cbase + (uint64_t)cl_before;
+    const bool cmove = first && cbase != C1_NOSLOT;  // closed rows are copied (else only dropped)
     const uint64_t lt = (1ULL << lane) - 1;
     int nh = 0, nhc = 0;
     for (int64_t r0 = wave * 64; r0 < nrow; r0 += NT) {
@@ -2315,7 +2437,7 @@ __global__ __launch_bounds__(NT, WPE) void k_c1v_merge(
         if (row_id(row, &id, &h)) e = c1_find_id<ID>(ids, id, h >> (32 - log2H), H);
       }
       const uint64_t bc = __ballot(cl);
-      if (cl) {  // (the query's HAVING alone: the merge's copy never carries pull / retention / FINAL bounds)
+      if (cl && cmove) {  // (the query's HAVING alone: the merge's copy never carries pull / retention / FINAL bounds)
         uint64_t* cd = closed + (ccur + __popcll(bc & lt)) * q.sw;
         for (int k = 0; k < q.sw; k++) cd[k] = row[k];
         nhc += having_ok_words(q.having.a.w_val >= 0 ? row[q.having.a.w_val] : 0,
@@ -2733,7 +2855,7 @@ khip_status c1_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t* 
                          (const ulonglong2*)s.srec.p, pass == 0 ? 1 : 0, s.buf[0].as<uint64_t>(), s.buf[1].as<uint64_t>(),
                          s.sel.as<uint8_t>(), s.cnt.as<int64_t>(), s.newcnt.as<unsigned long long>(),
                          s.fail.as<uint8_t>(), s.ctr.as<unsigned long long>() + 2, close0, s.closed.as<uint64_t>(),
-                         s.closed_ctr.as<unsigned long long>(), ci,
+                         s.closed_ctr.as<unsigned long long>(), (unsigned long long)s.closed_cap, ci,
                          s.hnew.as<unsigned long long>(), s.ctr.as<unsigned long long>() + 12, s.prn.as<uint32_t>(), dbg);
     }
     for (int idw = wide ? 1 : 0; idw < 2 && !val; idw++) {
@@ -2745,7 +2867,7 @@ khip_status c1_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t* 
                          s.srec.as<uint64_t>(), pass == 0 ? 1 : 0, s.buf[0].as<uint64_t>(), s.buf[1].as<uint64_t>(),
                          s.sel.as<uint8_t>(), s.cnt.as<int64_t>(), s.newcnt.as<unsigned long long>(),
                          s.fail.as<uint8_t>(), s.ctr.as<unsigned long long>() + 2, close0, s.closed.as<uint64_t>(),
-                         s.closed_ctr.as<unsigned long long>(), ci,
+                         s.closed_ctr.as<unsigned long long>(), (unsigned long long)s.closed_cap, ci,
                          s.hnew.as<unsigned long long>(), s.ctr.as<unsigned long long>() + 12, s.prn.as<uint32_t>(),
                          (const uint32_t*)srecT, dbg);
     }
@@ -2817,11 +2939,29 @@ khip_status c1_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t* 
                 ph[4] / g);
       }
     }
+    if (c2[2] & C1_FATAL)  // (cannot happen: the store holds every live row)
+      return fail(KHIP_E_DEVICE, "the closed store's capacity would be exceeded by a merge's closed rows");
     added_total += (int64_t)c2[0];
+    if (c2[1] != 0) {
+      host_fail.resize(P);
+      KHIP_TRY_HIP(hipMemcpy(host_fail.data(), s.fail.p, P, hipMemcpyDeviceToHost));
+    }
+#ifdef KHIP_TUNING
+    if (knob("KHIP_C1_TRACE", 0) != 0) {  // one line per pass: the tests' witness that a push was retried
+      int64_t nsub = 0, ft = 0, fr = 0;
+      if (wk)
+        for (const uint32_t x : work) nsub += ((x >> 16) & 0xF) != 0;
+      if (c2[1] != 0)
+        for (int p = 0; p < P; p++) ft += (host_fail[p] & 1) != 0, fr += (host_fail[p] & 2) != 0;
+      fprintf(stderr,
+              "[c1 trace] val=%d P=%d cmax=%lld log2H=%d pass=%d items=%lld sub_items=%lld failed=%llu fail_table=%lld "
+              "fail_region=%lld closed_before=%lld closed_after=%llu\n",
+              val ? 1 : 0, P, (long long)cq.cmax, val ? v_log2H : log2H, pass, (long long)nwork, (long long)nsub, c2[1],
+              (long long)ft, (long long)fr, (long long)s.closed_n, s.pinfo.as<unsigned long long>()[58]);
+    }
+#endif
     if (c2[1] == 0) break;
     if (pass > 24) return fail(KHIP_E_DEVICE, "partitioned aggregation could not place the batch");
-    host_fail.resize(P);
-    KHIP_TRY_HIP(hipMemcpy(host_fail.data(), s.fail.p, P, hipMemcpyDeviceToHost));
     KHIP_TRY_HIP(hipMemsetAsync(s.fail.p, 0, P, a->stream));
     bool grow = false;
     plist.clear();

@@ -160,6 +160,20 @@ def test_c1_sub_passes_and_region_growth(prod, orc):
     assert kt["c1_pushes"] == 1, kt
 
 
+def test_c1_evict_and_retry_release(prod, orc):
+    """The shipped library (no knobs) evicting and retrying in one push, as test_gpu_c1_retry.py's
+    region case at the release table size: hint 2^21 gives 2048 partitions of 4096-row regions and
+    an LDS table of 3072 groups.  Push 1 leaves ~980 (W0) + ~200 (W1) groups per partition (2.4 M,
+    under the 3.1 M at which partitions split); push 2 brings ~4300 new ones per partition (8.8 M)
+    and closes W0: every partition overflows the table on pass 0, on pass 1 the first sub-item fits
+    its region and the second does not, pass 2 runs after the regrow; push 3 merges that state and
+    closes W1.  The release build has no trace, so that the retry path is reached holds by
+    construction (the tuning build with default knobs shows these passes on the same shape)."""
+    from test_gpu_c1_retry import run_three_pushes
+    case = dict(hint=1 << 21, w=(980, 200, 4300), changes=False)
+    run_three_pushes(prod, orc, "release", case)
+
+
 def test_c1_wide_records(prod, orc):
     """Keys spread over 2^53 (a bijection of dense card ids): the key range needs the wide records
     (64-bit key hash + u32 ts word); the first push declines the compact format and is redone with

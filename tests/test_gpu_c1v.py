@@ -170,8 +170,13 @@ def test_c1v_declines(prod, orc):
 
 
 def test_c1v_many_groups_subpasses(prod, orc):
-    """More groups per partition than the merge's table takes at the hinted size: sub-pass
-    retries (split by key, so a pane and its windows stay together) and region growth."""
+    """More entries per partition than the merge's table takes.  What the tuning build's pass trace
+    shows for this workload: the hint gives 256 partitions, fewer than the pipeline takes, so push 1
+    runs the general path (and splits the partitions to 4096); push 2 runs the pipeline with a
+    2^10-entry table, 3669 of the 4096 partitions overflow it on pass 0 (a key's panes and windows
+    share the table) and pass 1 places them with 2 sub-passes each, split by key so a pane and its
+    windows stay together.  No region grows and no window closes (grace 30 s): eviction with
+    retries is test_gpu_c1_retry.py's."""
     rng = np.random.default_rng(9)
     batches = _batches(rng, "all_i32", 2, 1_000_000, 900_000, 20_000)
     kt = _run(prod, orc, "all_i32", "hop3", batches, hint=1 << 16)

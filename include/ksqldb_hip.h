@@ -43,7 +43,12 @@ typedef int32_t khip_status;
 #define KHIP_E_NOMEM (-2)       /* device or host allocation failed                         */
 #define KHIP_E_DEVICE (-3)      /* HIP runtime error                                         */
 #define KHIP_E_UNSUPPORTED (-4) /* descriptor valid for ksqlDB but not for this path: the
-                                   caller keeps the reference CPU builder for this query    */
+                                   caller keeps the reference CPU builder for this query.
+                                   LATEST_BY_OFFSET / EARLIEST_BY_OFFSET: with SESSION
+                                   windows, KHIP_FLAG_TABLE_SOURCE, a HAVING on the offset
+                                   aggregate itself, more user + hidden sequence columns
+                                   than 8, and khip_agg_push_shuffled on such a handle; the
+                                   N forms (arrays) are never routed here                   */
 #define KHIP_E_BUFFER (-5)      /* caller-provided output buffer too small                  */
 #define KHIP_E_COMM (-6)        /* RCCL error                                                */
 #define KHIP_E_STATE (-7)       /* call not valid in the handle's current state             */
@@ -81,6 +86,18 @@ typedef int32_t khip_status;
 #define KHIP_AGG_MIN 3
 #define KHIP_AGG_MAX 4
 #define KHIP_AGG_AVG 5
+/* LATEST_BY_OFFSET(col[, ignoreNulls]) / EARLIEST_BY_OFFSET(col[, ignoreNulls]), scalar forms:
+ * function/udaf/offset/LatestByOffset.java:87-146 (latestT), EarliestByOffset.java:85-158
+ * (earliestT), KudafByOffsetUtils.java:77-104 (the sequence comparators).  The value of the
+ * group's last / first record in arrival order (row order within a push, push order across pushes)
+ * whose argument is not NULL; with KHIP_AGG_KEEP_NULLS (ignoreNulls = false) the argument of the
+ * last / first record, NULL included.  The result has the argument's type and its exact bits (a
+ * DOUBLE keeps its NaN payload and -0.0).  Not with SESSION windows, KHIP_FLAG_TABLE_SOURCE, as
+ * the HAVING aggregate, or through khip_agg_push_shuffled: KHIP_E_UNSUPPORTED. */
+#define KHIP_AGG_LATEST_BY_OFFSET 6
+#define KHIP_AGG_EARLIEST_BY_OFFSET 7
+/* OR-ed into khip_agg_spec.kind of the two kinds above: ignoreNulls = false */
+#define KHIP_AGG_KEEP_NULLS 0x100
 
 /* Where a batch's column pointers live. */
 #define KHIP_MEM_HOST 0
@@ -200,7 +217,7 @@ typedef struct khip_having {
 } khip_having;
 
 typedef struct khip_agg_spec {
-  int32_t kind;    /* KHIP_AGG_*                                                      */
+  int32_t kind;    /* KHIP_AGG_* (the offset kinds: | KHIP_AGG_KEEP_NULLS)              */
   int32_t arg_col; /* value column index (ignored for COUNT_STAR)                     */
 } khip_agg_spec;
 

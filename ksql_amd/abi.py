@@ -27,7 +27,10 @@ KHIP_E_BUFFER = -5
 WINDOW = {"NONE": 0, "TUMBLING": 1, "HOPPING": 2, "SESSION": 3}
 KEY = {"INT64": 0, "UTF8": 1}
 TYPE = {"INT32": 0, "INT64": 1, "DOUBLE": 2}
-AGG = {"COUNT_STAR": 0, "COUNT": 1, "SUM": 2, "MIN": 3, "MAX": 4, "AVG": 5}
+AGG_KEEP_NULLS = 0x100  # KHIP_AGG_KEEP_NULLS: ignoreNulls = false, OR-ed into the two offset kinds
+AGG = {"COUNT_STAR": 0, "COUNT": 1, "SUM": 2, "MIN": 3, "MAX": 4, "AVG": 5,
+       "LATEST_BY_OFFSET": 6, "EARLIEST_BY_OFFSET": 7,
+       "LATEST_BY_OFFSET_NULLS": 6 | AGG_KEEP_NULLS, "EARLIEST_BY_OFFSET_NULLS": 7 | AGG_KEEP_NULLS}
 OP = {"GT": 0, "GE": 1, "LT": 2, "LE": 3, "EQ": 4, "NE": 5}
 JOIN = {"LEFT": 0, "INNER": 1}
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -387,7 +390,7 @@ def result_types(desc):
             out.append(TYPE["INT64"])
         elif k == AGG["AVG"]:
             out.append(TYPE["DOUBLE"])
-        else:
+        else:  # SUM / MIN / MAX, and LATEST / EARLIEST_BY_OFFSET (with or without AGG_KEEP_NULLS)
             out.append(desc.col_types[desc.aggs[i].arg_col])
     return out
 

@@ -24,6 +24,8 @@
 //                 row (no spin, no fence) → agent-scope atomics for the state
 //   k_finalize  : turn this batch's claim references into resident (key, ws)
 //   failures (probe budget exhausted) are resumed after a table doubling, exactly.
+//   [LATEST / EARLIEST_BY_OFFSET] k_off_iota before, a k_off_resolve_* kernel after the engine
+//                 (either engine): see "offset aggregates" below.
 #include <algorithm>
 #include <cstring>
 #include <numeric>
@@ -406,6 +408,72 @@ __global__ __launch_bounds__(256) void k_compact(const uint64_t* __restrict__ ta
       for (int w = 0; w < sw; w++) o[w] = s[w];
     }
     __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------- offset aggregates
+// LATEST_BY_OFFSET / EARLIEST_BY_OFFSET (khip_agg_internal.hpp OffResolve).  Per push: k_off_iota
+// writes the hidden sequence column; the engine keeps MAX / MIN of it per group in whatever order
+// it applies the records; a resolve kernel then turns the sequence words won by this push into
+// values, before anything reads the rows.  Groups won by earlier pushes are left alone, which keeps
+// EARLIEST stable and LATEST independent of how the stream is cut into pushes.
+
+__global__ __launch_bounds__(256) void k_off_iota(int64_t* __restrict__ seq, int64_t n, int64_t base) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    seq[i] = base + i;
+}
+
+// Partitioned engine: a block per partition; only partitions the push's records reached are read
+// (k_part_chg's test: prn after a pipeline push, else the scatter's partition bases), the rows of
+// their current buffer.
+__global__ __launch_bounds__(256) void k_off_resolve_part(uint64_t* __restrict__ b0, uint64_t* __restrict__ b1,
+                                                          const uint8_t* __restrict__ sel,
+                                                          const int64_t* __restrict__ cnt, int64_t cmax, int sw,
+                                                          const int64_t* __restrict__ pbase,
+                                                          const uint32_t* __restrict__ prn, OffResolve q) {
+  const int64_t p = blockIdx.x;
+  if (prn ? prn[p] == 0 : pbase[p + 1] == pbase[p]) return;
+  uint64_t* rows = (sel[p] ? b1 : b0) + (uint64_t)p * cmax * sw;
+  const int64_t n = cnt[p] < cmax ? cnt[p] : cmax;
+  for (int64_t r = threadIdx.x; r < n; r += 256) off_resolve_row(rows + r * sw, q, -1);
+}
+
+// Rows [r0, r1) of a flat row array (the closed store's rows appended by this push).
+__global__ __launch_bounds__(256) void k_off_resolve_rows(uint64_t* __restrict__ rows, int64_t r0, int64_t r1, int sw,
+                                                          OffResolve q) {
+  for (int64_t r = r0 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < r1; r += (int64_t)gridDim.x * blockDim.x)
+    off_resolve_row(rows + r * sw, q, -1);
+}
+
+// Global-atomic engine, after k_finalize: one thread per accepted record finds the resident slots
+// of its (key, window)s again and stores where the slot's sequence word is its own.  Work scales
+// with the push (<= fan-out probes per record), not with the table.
+__global__ __launch_bounds__(256) void k_off_resolve_probe(ApplyParams p, const int64_t* __restrict__ hkeys,
+                                                           const int64_t* __restrict__ keys,
+                                                           const int64_t* __restrict__ ts,
+                                                           const uint8_t* __restrict__ kv,
+                                                           const uint8_t* __restrict__ rv, int64_t n,
+                                                           uint64_t* __restrict__ table, uint64_t mask, OffResolve q) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= n || !bit_get(kv, i) || !bit_get(rv, i)) return;
+  const int64_t t = ts[i];
+  if (t < 0) return;
+  const int64_t key = keys[i], hkey = hkeys[i], seq = q.base + i;
+  const int64_t ws0 = p.windowed ? first_window_start(t, p.size, p.adv) : 0;
+  const int64_t wsN = p.windowed ? t : 0;
+  const int64_t step = p.windowed ? p.adv : 1;
+  for (int64_t ws = ws0; ws <= wsN; ws += step) {
+    uint64_t slot = group_hash(hkey, ws) & mask;
+    for (int probe = 0; probe < MAX_PROBE; probe++) {
+      uint64_t* s = table + slot * (uint64_t)p.slot_words;
+      const int64_t w1 = (int64_t)s[1];
+      if (w1 == EMPTY_WS) break;  // (a late window of this record may have no group)
+      if (w1 == ws && (int64_t)s[0] == key) {
+        off_resolve_row(s, q, seq);
+        break;
+      }
+      slot = (slot + 1) & mask;
+    }
   }
 }
 
@@ -1066,13 +1134,52 @@ void dict_release(KeyDict& d) {
 
 using namespace khip;
 
+static inline int agg_base_kind(int32_t kind) { return kind & ~KHIP_AGG_KEEP_NULLS; }
+static inline bool agg_is_offset(int32_t kind) {
+  const int b = agg_base_kind(kind);
+  return b == KHIP_AGG_LATEST_BY_OFFSET || b == KHIP_AGG_EARLIEST_BY_OFFSET;
+}
+
 static khip_status plan_state(khip_agg* a) {
   const khip_agg_desc& d = a->desc;
   int word = 3;  // w0, w1, rowtime
   int w_star = -1;
-  std::vector<int> w_cnt(d.n_cols, -1), w_sum(d.n_cols, -1), w_min(d.n_cols, -1), w_max(d.n_cols, -1);
+  // offset aggregates: the hidden sequence columns (one per argument column of an ignore-nulls
+  // form, whose validity it takes, and one without validity for the KEEP_NULLS forms), and first
+  // in the row the value / null words no update op writes (the sequence words come last: the
+  // engines keep every word up to the highest op word)
+  a->n_hidden = 0;
+  a->offs = OffResolve{};
+  a->out_off.assign(d.n_aggs, -1);
+  std::vector<int> off_hid(d.n_aggs, -1);
   for (int i = 0; i < d.n_aggs; i++) {
     const khip_agg_spec& s = a->aggs[i];
+    if (!agg_is_offset(s.kind)) continue;
+    const int src = (s.kind & KHIP_AGG_KEEP_NULLS) ? -1 : s.arg_col;
+    int h = -1;
+    for (int k = 0; k < a->n_hidden; k++)
+      if (a->hid_src[k] == src) h = k;
+    if (h < 0) {
+      if (d.n_cols + a->n_hidden >= MAX_COLS)
+        return fail(KHIP_E_UNSUPPORTED, "offset aggregates: value columns + hidden sequence columns above 8");
+      h = a->n_hidden++;
+      a->hid_src[h] = src;
+    }
+    off_hid[i] = d.n_cols + h;
+    OffSpec o{};
+    o.col = (int8_t)s.arg_col;
+    o.type = (int8_t)a->col_types[s.arg_col];
+    o.w_val = (int16_t)word++;
+    o.w_null = (s.kind & KHIP_AGG_KEEP_NULLS) ? (int16_t)word++ : (int16_t)-1;
+    o.w_seq = -1;
+    a->out_off[i] = a->offs.n;
+    a->offs.a[a->offs.n++] = o;
+  }
+  const int nc = d.n_cols + a->n_hidden;  // internal argument columns
+  std::vector<int> w_cnt(nc, -1), w_sum(nc, -1), w_min(nc, -1), w_max(nc, -1);
+  for (int i = 0; i < d.n_aggs; i++) {
+    const khip_agg_spec& s = a->aggs[i];
+    if (agg_is_offset(s.kind)) continue;
     if (s.kind == KHIP_AGG_COUNT_STAR) {
       if (w_star < 0) w_star = word++;
       continue;
@@ -1085,6 +1192,14 @@ static khip_status plan_state(khip_agg* a) {
     if (s.kind == KHIP_AGG_MIN && w_min[c] < 0) w_min[c] = word++;
     if (s.kind == KHIP_AGG_MAX && w_max[c] < 0) w_max[c] = word++;
   }
+  for (int i = 0; i < d.n_aggs; i++) {  // latest = MAX(seq), earliest = MIN(seq); no non-null count:
+    if (off_hid[i] < 0) continue;       // the initial value itself says "no record yet"
+    const int h = off_hid[i];
+    const bool latest = agg_base_kind(a->aggs[i].kind) == KHIP_AGG_LATEST_BY_OFFSET;
+    int& w = latest ? w_max[h] : w_min[h];
+    if (w < 0) w = word++;
+    a->offs.a[a->out_off[i]].w_seq = (int16_t)w;
+  }
   if (word > 32) return fail(KHIP_E_UNSUPPORTED, "too many aggregate state words (max 29)");
   a->sw = (int)next_pow2(std::max(word, 4));
   ApplyParams& p = a->ap;
@@ -1093,8 +1208,8 @@ static khip_status plan_state(khip_agg* a) {
   p.size = d.size_ms;
   p.adv = d.advance_ms;
   p.grace = a->grace;
-  p.n_cols = d.n_cols;
-  for (int c = 0; c < d.n_cols; c++) p.col_type[c] = a->col_types[c];
+  p.n_cols = nc;
+  for (int c = 0; c < nc; c++) p.col_type[c] = c < d.n_cols ? a->col_types[c] : KHIP_TYPE_INT64;
   int n = 0;
   auto add = [&](int8_t kind, int col, int w) {
     p.ops[n].kind = kind;
@@ -1103,9 +1218,9 @@ static khip_status plan_state(khip_agg* a) {
     n++;
   };
   if (w_star >= 0) add(OP_INC, 0, w_star);
-  for (int c = 0; c < d.n_cols; c++) {
+  for (int c = 0; c < nc; c++) {
     if (w_cnt[c] >= 0) add(OP_INC_VALID, c, w_cnt[c]);
-    if (w_sum[c] >= 0) add(a->col_types[c] == KHIP_TYPE_DOUBLE ? OP_ADD_F64 : OP_ADD_I64, c, w_sum[c]);
+    if (w_sum[c] >= 0) add(p.col_type[c] == KHIP_TYPE_DOUBLE ? OP_ADD_F64 : OP_ADD_I64, c, w_sum[c]);
     if (w_min[c] >= 0) add(OP_MIN, c, w_min[c]);
     if (w_max[c] >= 0) add(OP_MAX, c, w_max[c]);
   }
@@ -1113,7 +1228,7 @@ static khip_status plan_state(khip_agg* a) {
   for (int w = 0; w < 32; w++) a->init.w[w] = 0;
   a->init.w[1] = EMPTY_WS;
   a->init.w[2] = INT64_MIN;
-  for (int c = 0; c < d.n_cols; c++) {
+  for (int c = 0; c < nc; c++) {
     if (w_min[c] >= 0) a->init.w[w_min[c]] = INT64_MAX;
     if (w_max[c] >= 0) a->init.w[w_max[c]] = INT64_MIN;
   }
@@ -1121,16 +1236,18 @@ static khip_status plan_state(khip_agg* a) {
   for (int i = 0; i < d.n_aggs; i++) {
     const khip_agg_spec& s = a->aggs[i];
     AggOut o{};
-    o.kind = s.kind;
+    o.kind = agg_base_kind(s.kind);
     o.type = s.kind == KHIP_AGG_COUNT_STAR ? KHIP_TYPE_INT64 : a->col_types[s.arg_col];
-    o.w_cnt = s.kind == KHIP_AGG_COUNT_STAR ? -1 : w_cnt[s.arg_col];
-    switch (s.kind) {
+    o.w_cnt = s.kind == KHIP_AGG_COUNT_STAR ? -1 : (agg_is_offset(s.kind) ? -1 : w_cnt[s.arg_col]);
+    switch (o.kind) {
       case KHIP_AGG_COUNT_STAR: o.w_val = w_star; break;
       case KHIP_AGG_COUNT: o.w_val = w_cnt[s.arg_col]; break;
       case KHIP_AGG_SUM:
       case KHIP_AGG_AVG: o.w_val = w_sum[s.arg_col]; break;
       case KHIP_AGG_MIN: o.w_val = w_min[s.arg_col]; break;
       case KHIP_AGG_MAX: o.w_val = w_max[s.arg_col]; break;
+      case KHIP_AGG_LATEST_BY_OFFSET:
+      case KHIP_AGG_EARLIEST_BY_OFFSET: o.w_val = a->offs.a[a->out_off[i]].w_val; break;  // (decoded by emit_snapshot)
     }
     a->outs.push_back(o);
   }
@@ -1291,11 +1408,27 @@ khip_status khip_agg_create(const khip_agg_desc* desc, khip_agg** out) {
   for (int c = 0; c < d.n_cols; c++)
     if (d.col_types[c] < KHIP_TYPE_INT32 || d.col_types[c] > KHIP_TYPE_DOUBLE)
       return fail(KHIP_E_INVALID, "column type");
+  bool has_offset = false;
   for (int i = 0; i < d.n_aggs; i++) {
     const khip_agg_spec& s = d.aggs[i];
-    if (s.kind < KHIP_AGG_COUNT_STAR || s.kind > KHIP_AGG_AVG) return fail(KHIP_E_INVALID, "aggregate kind");
+    const int bk = agg_base_kind(s.kind);
+    if (bk < KHIP_AGG_COUNT_STAR || bk > KHIP_AGG_EARLIEST_BY_OFFSET) return fail(KHIP_E_INVALID, "aggregate kind");
+    if ((s.kind & KHIP_AGG_KEEP_NULLS) && !agg_is_offset(s.kind))
+      return fail(KHIP_E_INVALID, "KHIP_AGG_KEEP_NULLS on an aggregate other than LATEST / EARLIEST_BY_OFFSET");
     if (s.kind != KHIP_AGG_COUNT_STAR && (s.arg_col < 0 || s.arg_col >= d.n_cols))
       return fail(KHIP_E_INVALID, "aggregate argument column");
+    has_offset = has_offset || agg_is_offset(s.kind);
+  }
+  if (has_offset) {
+    // merged by sequence (Udaf.merge) in the reference: not on the device
+    if (d.window_kind == KHIP_WINDOW_SESSION)
+      return fail(KHIP_E_UNSUPPORTED, "LATEST / EARLIEST_BY_OFFSET with SESSION windows");
+    // not TableUdafs: the reference rejects them on a table source as it rejects MIN/MAX
+    if (d.flags & KHIP_FLAG_TABLE_SOURCE)
+      return fail(KHIP_E_UNSUPPORTED, "LATEST / EARLIEST_BY_OFFSET cannot be applied to a table source");
+    if (d.has_having && d.having.agg_index >= 0 && d.having.agg_index < d.n_aggs &&
+        agg_is_offset(d.aggs[d.having.agg_index].kind))
+      return fail(KHIP_E_UNSUPPORTED, "HAVING on a LATEST / EARLIEST_BY_OFFSET aggregate");
   }
   if (d.emit != KHIP_EMIT_CHANGES && d.emit != KHIP_EMIT_FINAL) return fail(KHIP_E_INVALID, "emit strategy");
   if (d.flags & KHIP_FLAG_TABLE_SOURCE) {  // table aggregation: undoable aggregates, no windows
@@ -1508,6 +1641,7 @@ khip_status khip_agg_push_shuffled(khip_agg* a, const khip_shuffle* sh, const ui
   if (a->engine == 3) return fail(KHIP_E_STATE, "table-source aggregation: use khip_agg_push_table");
   if (a->desc.time_domain == KHIP_TIME_PARTITION)
     return fail(KHIP_E_UNSUPPORTED, "KHIP_TIME_PARTITION: received rows carry no source partition");
+  if (a->offs.n) return fail(KHIP_E_UNSUPPORTED, "LATEST / EARLIEST_BY_OFFSET: shuffled rows carry no arrival order");
   const bool sup = a->desc.time_domain == KHIP_TIME_SUPPLIED;
   const int rw = khip_shuffle_row_words(sh);
   if (sup && rw != 3 + nc)
@@ -1670,6 +1804,30 @@ khip_status khip_agg_push_table(khip_agg* a, const khip_batch* b, const khip_tab
   return KHIP_OK;
 }
 
+// Offset aggregates after one partitioned push slice (cols: the slice's columns; its sequence
+// numbers are [base, base + m)): the partitions the slice reached, and the rows it appended to the
+// closed store (a window can be updated and closed by the same push).
+static khip_status off_resolve_part(khip_agg* a, const ColPtrs& cols, int64_t base, int64_t m, int64_t closed0) {
+  PartState& s = a->part;
+  OffResolve q = a->offs;
+  for (int c = 0; c < a->desc.n_cols; c++) {
+    q.data[c] = cols.data[c];
+    q.valid[c] = cols.valid[c];
+  }
+  q.base = base;
+  q.rows = m;
+  hipLaunchKernelGGL(k_off_resolve_part, dim3((unsigned)s.P), dim3(256), 0, a->stream, s.buf[0].as<uint64_t>(),
+                     s.buf[1].as<uint64_t>(), s.sel.as<uint8_t>(), s.cnt.as<int64_t>(), s.cmax, a->sw,
+                     s.pbase.as<int64_t>(), s.last_c1 ? s.prn.as<uint32_t>() : (const uint32_t*)nullptr, q);
+  if (s.closed_n > closed0)
+    hipLaunchKernelGGL(k_off_resolve_rows, dim3(grid_for(s.closed_n - closed0, 256, 4096)), dim3(256), 0, a->stream,
+                       s.closed.as<uint64_t>(), closed0, s.closed_n, a->sw, q);
+  KHIP_TRY_HIP(hipGetLastError());
+  // the caller's columns (and a host batch's staging copies) are only valid until the push returns
+  KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
+  return KHIP_OK;
+}
+
 khip_status khip_agg_push(khip_agg* a, const khip_batch* b, khip_batch_stats* stats) {
   clear_error();
   if (!a || !b) return fail(KHIP_E_INVALID, "null argument");
@@ -1719,6 +1877,16 @@ khip_status khip_agg_push(khip_agg* a, const khip_batch* b, khip_batch_stats* st
   ColPtrs cols{};
   int64_t key_bytes_total = 0;
   KHIP_TRY(resolve_batch(a, b, &keys, &ts, &kv, &rv, &koff, &kbytes, &cols, &key_bytes_total));
+  if (a->n_hidden) {  // offset aggregates: the hidden sequence columns (one iota, the arguments' validity)
+    KHIP_TRY(a->seqbuf.ensure((size_t)n * 8));
+    hipLaunchKernelGGL(k_off_iota, dim3(grid_for(n, 256, 4096)), dim3(256), 0, a->stream, a->seqbuf.as<int64_t>(), n,
+                       a->seq_base);
+    KHIP_TRY_HIP(hipGetLastError());
+    for (int h = 0; h < a->n_hidden; h++) {
+      cols.data[a->desc.n_cols + h] = a->seqbuf.p;
+      cols.valid[a->desc.n_cols + h] = a->hid_src[h] >= 0 ? cols.valid[a->hid_src[h]] : nullptr;
+    }
+  }
   const bool pdomain = a->desc.time_domain == KHIP_TIME_PARTITION;
   // (SESSION windows close sessions themselves: sess_push)
   if (final_emit && !pdomain && !sctx && a->engine != 2) KHIP_TRY(emit_final_lost(a, ts, kv, rv, n, a->st_before, nullptr));
@@ -1784,12 +1952,16 @@ khip_status khip_agg_push(khip_agg* a, const khip_batch* b, khip_batch_stats* st
     for (int64_t off = 0; off < n; off += slice) {
       const int64_t m = std::min(slice, n - off);
       ColPtrs cs = cols;
-      for (int c = 0; c < a->desc.n_cols; c++) {
-        cs.data[c] = (const char*)cols.data[c] + off * (a->col_types[c] == KHIP_TYPE_INT32 ? 4 : 8);
+      for (int c = 0; c < a->ap.n_cols; c++) {  // (the hidden sequence columns too: the base advances per slice)
+        cs.data[c] = (const char*)cols.data[c] + off * (a->ap.col_type[c] == KHIP_TYPE_INT32 ? 4 : 8);
         if (cs.valid[c]) cs.valid[c] += off / 8;
       }
+      const int64_t closed0 = a->part.closed_n;
       KHIP_TRY(part_push(a, m, keys + off, ts + off, kv ? kv + off / 8 : nullptr, rv ? rv + off / 8 : nullptr, cs,
                          tot, st_at ? st_at + off : nullptr));
+      // offset aggregates: the slice's winning sequence numbers become values, before the closed
+      // store is purged and before anything reads rows or changes
+      if (a->offs.n) KHIP_TRY(off_resolve_part(a, cs, a->seq_base + off, m, closed0));
     }
     a->occ += tot[P_NEW];
     if (a->profile) {  // events of the last slice
@@ -1859,7 +2031,21 @@ khip_status khip_agg_push(khip_agg* a, const khip_batch* b, khip_batch_stats* st
   }
   a->times.apply_ms += apply_ms;
   a->times.finalize_ms += fin_ms;
+  if (a->offs.n) {  // offset aggregates: every record re-probes its groups (the table is final now)
+    OffResolve q = a->offs;
+    for (int c = 0; c < a->desc.n_cols; c++) {
+      q.data[c] = cols.data[c];
+      q.valid[c] = cols.valid[c];
+    }
+    q.base = a->seq_base;
+    q.rows = n;
+    hipLaunchKernelGGL(k_off_resolve_probe, dim3(grid_for(n, 256)), dim3(256), 0, a->stream, a->ap, hkeys, keys, ts,
+                       kv, rv, n, a->table.as<uint64_t>(), (uint64_t)(a->cap - 1), q);
+    KHIP_TRY_HIP(hipGetLastError());
+    KHIP_TRY_HIP(hipStreamSynchronize(a->stream));  // (a host batch's staging buffers are reused by the next push)
   }
+  }
+  a->seq_base += n;
   if (a->engine == 1) {  // the other engines brought it back with their end-of-push counters
     KHIP_TRY_HIP(hipMemcpyAsync(&a->host_stream_time, a->stream_time.p, 8, hipMemcpyDeviceToHost, a->stream));
     KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
@@ -2004,6 +2190,8 @@ static khip_status compact_rows(khip_agg* a, const khip_having* h, std::vector<u
   if (h) {
     if (h->agg_index < 0 || h->agg_index >= a->desc.n_aggs) return fail(KHIP_E_INVALID, "having agg index");
     if (h->op < KHIP_OP_GT || h->op > KHIP_OP_NE) return fail(KHIP_E_INVALID, "having op");
+    if (agg_is_offset(a->aggs[h->agg_index].kind))  // (decode_words does not know the offset kinds)
+      return fail(KHIP_E_UNSUPPORTED, "HAVING on a LATEST / EARLIEST_BY_OFFSET aggregate");
     hd.active = 1;
     hd.op = h->op;
     hd.a = a->outs[h->agg_index];
@@ -2181,6 +2369,15 @@ static khip_status emit_snapshot(khip_agg* a, const std::vector<uint64_t>& rows,
           else if (o.type == KHIP_TYPE_DOUBLE) dv = f64_from_order_key((int64_t)s[o.w_val]);
           else iv = (int64_t)s[o.w_val];
           break;
+        case KHIP_AGG_LATEST_BY_OFFSET:
+        case KHIP_AGG_EARLIEST_BY_OFFSET: {  // NULL: no record yet, or the winning row's NULL (KEEP_NULLS)
+          const OffSpec& f = a->offs.a[a->out_off[i]];
+          const int64_t none = o.kind == KHIP_AGG_LATEST_BY_OFFSET ? INT64_MIN : INT64_MAX;
+          if ((int64_t)s[f.w_seq] == none || (f.w_null >= 0 && s[f.w_null] != 0)) isnull = true;
+          else if (o.type == KHIP_TYPE_DOUBLE) memcpy(&dv, &s[f.w_val], 8);  // the bits: NaN payloads, -0.0
+          else iv = (int64_t)s[f.w_val];
+          break;
+        }
         case KHIP_AGG_AVG: {
           const int64_t c = (int64_t)s[o.w_cnt];
           if (c == 0) dv = 0.0;
@@ -2383,6 +2580,7 @@ khip_status khip_agg_reset(khip_agg* a) {
   KHIP_TRY_HIP(hipGetLastError());
   a->occ = 0;
   a->host_stream_time = -1;
+  a->seq_base = 0;
   return KHIP_OK;
 }
 
@@ -2414,7 +2612,7 @@ khip_status khip_agg_destroy(khip_agg* a) {
   DevBuf* bufs[] = {&a->table, &a->blockmax, &a->blockprefix, &a->partials, &a->resume, &a->counters,
                     &a->stream_time, &a->st_keys, &a->st_ts, &a->st_kv, &a->st_rv, &a->st_koff,
                     &a->st_kbytes, &a->kid, &a->khash, &a->chg, &a->lostbuf, &a->lostctr,
-                    &a->pst, &a->pst2, &a->st_col, &a->st_agg, &a->st_seen, &a->st_part};
+                    &a->pst, &a->pst2, &a->st_col, &a->st_agg, &a->st_seen, &a->st_part, &a->seqbuf};
   for (DevBuf* b : bufs) b->release();
   for (int c = 0; c < MAX_COLS; c++) {
     a->st_cols[c].release();

@@ -51,6 +51,27 @@ struct AggOut {
   int32_t w_cnt;  // non-null count word (-1 if none)
 };
 
+// LATEST_BY_OFFSET / EARLIEST_BY_OFFSET (khip_agg.hip "offset aggregates").  Arrival order is a
+// value: every row of a push carries seq = rows pushed before + row index in a hidden INT64
+// argument column, and the engines keep MAX(seq) / MIN(seq) per group like any other MAX / MIN.
+// One such aggregate: its sequence word (INT64_MIN / INT64_MAX = no record yet: NULL), its value
+// word (the argument's bits of the winning row) and, for the KEEP_NULLS forms, a null word (1 =
+// the winning row's argument was NULL; -1: none).  The value and null words are no update op's:
+// the engines carry them with the row, and the resolve kernels write them before a push returns.
+struct OffSpec {
+  int16_t w_seq, w_val, w_null;
+  int8_t col;   // the argument (user) column
+  int8_t type;  // its type
+};
+constexpr int MAX_OFFS = 16;
+struct OffResolve {
+  int32_t n;
+  OffSpec a[MAX_OFFS];
+  const void* data[MAX_COLS];  // the push's argument columns (user columns)
+  const uint8_t* valid[MAX_COLS];
+  int64_t base, rows;  // the push's sequence numbers are [base, base + rows)
+};
+
 struct HavingDev {
   int32_t active;
   int32_t op;
@@ -313,6 +334,26 @@ __device__ __forceinline__ int64_t load_col_raw(const ColPtrs& c, int32_t type, 
   return ((const int64_t*)c.data[col])[i];  // INT64, or DOUBLE bits
 }
 
+// Offset aggregates: the words of row s won by a record of this push (sequence in [base, base +
+// rows)) get that record's argument bits and null flag, gathered from the caller's column.  `only`
+// >= 0: just the aggregates whose sequence word equals it (the global-atomic engine's re-probe: one
+// thread per record, so two records winning different aggregates of one group write different
+// words).  Plain vector loads and stores: the sequence words were produced by earlier kernels on the
+// stream (the launch boundary is the fence).
+__device__ __forceinline__ void off_resolve_row(uint64_t* s, const OffResolve& q, int64_t only) {
+  for (int k = 0; k < q.n; k++) {
+    const OffSpec o = q.a[k];
+    const int64_t seq = (int64_t)s[o.w_seq];
+    const uint64_t i = (uint64_t)seq - (uint64_t)q.base;  // (the "none yet" values land far outside)
+    if (i >= (uint64_t)q.rows || (only >= 0 && seq != only)) continue;
+    int64_t v;
+    if (o.type == KHIP_TYPE_INT32) v = (int64_t)((const int32_t*)q.data[o.col])[i];
+    else v = ((const int64_t*)q.data[o.col])[i];  // INT64, or DOUBLE bits
+    s[o.w_val] = (uint64_t)v;
+    if (o.w_null >= 0) s[o.w_null] = bit_get(q.valid[o.col], (int64_t)i) ? 0ULL : 1ULL;
+  }
+}
+
 // One aggregate's result from its value word and non-null count word.  Returns false for
 // SQL NULL; sets *iv for integer results, *dv for DOUBLE results.
 __device__ __forceinline__ bool decode_words(uint64_t val, uint64_t cntw, const AggOut& a, int64_t* iv, double* dv) {
@@ -561,6 +602,17 @@ struct khip_agg {
   ApplyParams ap{};
   InitWords init{};
   std::vector<AggOut> outs;
+  // ---- offset aggregates (LATEST_BY_OFFSET / EARLIEST_BY_OFFSET).  Internal argument columns =
+  // desc.n_cols user columns + n_hidden sequence columns (ap.n_cols, ap.col_type, ap.ops' col): all
+  // hidden columns read one iota buffer (seqbuf, seq_base + row); hidden column h takes the
+  // validity bitmap of user column hid_src[h] (the ignore-nulls forms) or none (-1: KEEP_NULLS).
+  // offs: one entry per offset aggregate of the query (out_off[i]: aggregate i's entry, or -1).
+  OffResolve offs{};
+  std::vector<int> out_off;
+  int n_hidden = 0;
+  int hid_src[MAX_COLS] = {};
+  DevBuf seqbuf;
+  int64_t seq_base = 0;  // rows pushed since the handle's creation or last reset
   int sw = 4;
   // table
   DevBuf table;

@@ -3555,7 +3555,7 @@ khip_status part_init(khip_agg* a, int64_t hint) {
   const bool meta = a->desc.window_kind == KHIP_WINDOW_HOPPING || s.vcols != 0;
   s.meta_word = meta ? 2 : -1;
   int w = meta ? 3 : 2;
-  for (int c = 0; c < MAX_COLS; c++) s.col_word[c] = (c < a->desc.n_cols && colref[c]) ? (int8_t)w++ : (int8_t)-1;
+  for (int c = 0; c < MAX_COLS; c++) s.col_word[c] = (c < a->ap.n_cols && colref[c]) ? (int8_t)w++ : (int8_t)-1;
   s.rw = (w + 1) & ~1;
   KHIP_TRY(s.sel.ensure(s.P));
   KHIP_TRY(s.fail.ensure(s.P));
@@ -3650,7 +3650,7 @@ static PartAggParams part_params(khip_agg* a) {
   q.dbg_mode = (int32_t)knob("KHIP_AGG_MODE", 0);
   q.log2P = s.log2P;
   q.cmax = s.cmax;
-  q.n_cols = a->desc.n_cols;
+  q.n_cols = a->ap.n_cols;  // (with the offset aggregates' hidden sequence columns)
   q.n_ops = a->ap.n_ops;
   for (int c = 0; c < MAX_COLS; c++) q.col_type[c] = a->ap.col_type[c];
   for (int o = 0; o < a->ap.n_ops; o++) q.ops[o] = a->ap.ops[o];
@@ -3946,7 +3946,7 @@ khip_status part_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t
   if (scat_lds > 64 * 1024)
     hipFuncSetAttribute((const void*)scat, hipFuncAttributeMaxDynamicSharedMemorySize, (int)scat_lds);
   hipLaunchKernelGGL(scat, dim3(nT), dim3(PT_THREADS), scat_lds, a->stream, keys, ts, kv, rv,
-                     cols, a->desc.n_cols, ct, n, tile, s.log2P - fbits, pad, nT,
+                     cols, a->ap.n_cols, ct, n, tile, s.log2P - fbits, pad, nT,
                      lvl2 ? s.hcoarse.as<uint32_t>() : s.hist.as<uint32_t>(), s.pbase.as<int64_t>(),
                      s.tileprefix.as<int64_t>(),
                      s.tilemax.as<int64_t>(), s.tilemin.as<int64_t>(), a->windowed, a->desc.size_ms,
@@ -3959,7 +3959,7 @@ khip_status part_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t
     auto sw_ = wu >= 4 ? k_part_scatter_w<4, W_NT> : k_part_scatter_w<2, W_NT>;
     const size_t sw_lds = stage_lds_bytes(nbins, 2 * wu * W_NT);
     if (sw_lds > 64 * 1024) hipFuncSetAttribute((const void*)sw_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sw_lds);
-    hipLaunchKernelGGL(sw_, dim3(nT), dim3(W_NT), sw_lds, a->stream, keys, ts, kv, rv, cols, a->desc.n_cols, ct, n, tile,
+    hipLaunchKernelGGL(sw_, dim3(nT), dim3(W_NT), sw_lds, a->stream, keys, ts, kv, rv, cols, a->ap.n_cols, ct, n, tile,
                        s.log2P - fbits, nT, lvl2 ? s.hcoarse.as<uint32_t>() : s.hist.as<uint32_t>(),
                        s.tileprefix.as<int64_t>(), s.tilemax.as<int64_t>(), s.tilemin.as<int64_t>(), a->windowed,
                        a->desc.size_ms, a->windowed ? a->desc.advance_ms : 1,

@@ -405,6 +405,9 @@ typedef struct khip_table_src {
  * value (key_valid 0 = NULL: the row joins no group, S/GroupByParamsFactory.java:92-100), row_valid
  * 0 = tombstone (the key is deleted), ts = ROWTIME (< 0: dropped), value columns = the aggregate
  * arguments.  Group row time = the largest ts of the records that added to or undid from it.
+ * Several records of one PRIMARY KEY inside a push are netted (the stored row undone once, the last
+ * row applied once); an intermediate row whose DOUBLE argument is +-Inf or NaN still leaves its
+ * group's SUM / AVG NaN, as its add and undo one after the other do (Inf - Inf).
  * stats: rows_accepted = source records applied, dropped_null_key = null PRIMARY KEY,
  * windows_applied = aggregate updates (adds + undos). */
 khip_status khip_agg_push_table(khip_agg* agg, const khip_batch* batch, const khip_table_src* src,

@@ -456,8 +456,14 @@ __global__ __launch_bounds__(256) void k_tagg_apply(TaggArgs A, const uint64_t* 
     // group and applies the new one; over the push these telescope: the stored row A0 is undone
     // once (at the first change's time), the last row applied once (at its time), and every
     // intermediate row's +x / −x cancel — its group only takes the row time (and exists: a group
-    // a row passed through stays, with its count back where it was).  Integer state is exact;
-    // DOUBLE sums differ from the one-by-one order only by rounding.  `upd` counts the
+    // a row passed through stays, with its count back where it was) and the delta x − x of the row
+    // against itself: 0 (nothing is added) for the counts, the integer sums and a finite DOUBLE, NaN
+    // for a DOUBLE ±Inf or NaN, whose add and undo do not cancel in the one-by-one order either
+    // (Inf − Inf: the group's sum stays NaN).  Integer state is exact.  DOUBLE sums of finite
+    // rows differ from the one-by-one order by rounding, and where the one-by-one sum − old + new
+    // passes through ±Inf on the way (an overflow that a later undo does not take back there: the
+    // sum stays Inf or NaN) the netted delta may stay finite; rows that are ±Inf or NaN themselves
+    // give the one-by-one result, as stored, last or intermediate row.  `upd` counts the
     // undo/apply operations of the one-by-one replay (the push's statistics).
     const TRow<NC> a0 = prev;  // the stored row
     const bool a0_live = (a0.flags & (TF_LIVE | TF_GVALID)) == (TF_LIVE | TF_GVALID);
@@ -470,8 +476,8 @@ __global__ __launch_bounds__(256) void k_tagg_apply(TaggArgs A, const uint64_t* 
       const TRow<NC> cur = rec_row<NC, U8>(rec, r, &t, &f);
       if (!(f & RF_ACC)) continue;
       if ((prev.flags & (TF_LIVE | TF_GVALID)) == (TF_LIVE | TF_GVALID)) {  // undo the previous row
-        if (!first)  // an intermediate row: its group's row time is max(apply, undo)
-          change(prev, false, prev, false, prev, t > t_app ? t : t_app, r_app);
+        if (!first)  // an intermediate row: its group's row time is max(apply, undo), and + x − x
+          change(prev, true, prev, true, prev, t > t_app ? t : t_app, r_app);
         upd++;
       }
       if (first) t_first = t;

@@ -1314,8 +1314,8 @@ khip_status emit_final_lost(khip_agg* a, const int64_t* ts, const uint8_t* kv, c
     KHIP_TRY(a->lostbuf.ensure((size_t)a->lost_cap * 16));
   }
   int64_t* seed = a->blockprefix.as<int64_t>() + nb;  // stream time before the batch
-  KHIP_TRY(a->part.pinfo.ensure(512));
-  int64_t* hs = a->part.pinfo.as<int64_t>() + 24;
+  KHIP_TRY(a->part.pinfo.ensure(sizeof(PushInfo)));
+  int64_t* hs = &a->part.info()->seed_st;
   hs[0] = seed_st;  // the stream time before the batch
   KHIP_TRY_HIP(hipMemcpyAsync(seed, hs, 8, hipMemcpyHostToDevice, a->stream));
   KHIP_TRY_HIP(hipMemsetAsync(a->lostctr.p, 0, 8, a->stream));
@@ -1614,8 +1614,8 @@ static khip_status resolve_batch(khip_agg* a, const khip_batch* b, const int64_t
 static khip_status supplied_advance(khip_agg* a) {
   if (a->sup_after > a->host_stream_time) {
     a->host_stream_time = a->sup_after;
-    KHIP_TRY(a->part.pinfo.ensure(512));
-    int64_t* hs = a->part.pinfo.as<int64_t>() + 25;
+    KHIP_TRY(a->part.pinfo.ensure(sizeof(PushInfo)));
+    int64_t* hs = &a->part.info()->sup_after;
     hs[0] = a->sup_after;
     KHIP_TRY_HIP(hipMemcpyAsync(a->stream_time.p, hs, 8, hipMemcpyHostToDevice, a->stream));
     KHIP_TRY_HIP(hipStreamSynchronize(a->stream));

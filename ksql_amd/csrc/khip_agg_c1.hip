@@ -58,32 +58,6 @@ constexpr int C1_SEGB = 7;       // the merge's segment lookup: one entry per 32
 constexpr int C1_SEGOF = 512;    // item (the finest that fits 512 entries; past 64K records: binary search)
 constexpr uint32_t C1_SENT = 0x80000000u;  // low word of a sentinel record (ts - T0 never is)
 
-// c1info (int64) slots
-enum {
-  CI_KMIN = 0,   // atomics (the scatters), reset by k_c1_check for the next push
-  CI_KMAX = 1,
-  CI_TFAIL = 2,  // some accepted ts - T0 outside int32 (k_c1_scatter)
-  CI_T0 = 3,     // time base (the scatters' block 0)
-  CI_GATE = 4,   // accepted (k_part_commit reads gate[4])
-  CI_WBASE = 5,  // smallest window index (records and live resident rows)
-  CI_WBITS = 6,
-  CI_ID32 = 7,   // identity mode: 1 = u32 (krel << wbits | wrel), 0 = u64 (krel << 32 | wrel)
-  CI_TMIN = 8,   // smallest accepted ts (row-time deltas are relative to it)
-  CI_TMAX = 9,
-  CI_KBITS = 10,
-  CI_NCHUNK = 11,  // refine work items
-  CI_KMINC = 12,   // kmin copied for the refine / merge
-  CI_WHI = 13,     // largest relative window index
-  CI_KRANGE = 14,
-  CI_WIDE = 15,    // records of this push: 1 = key hash + u32 ts words (the key range is too wide)
-  CI_REASON = 16,  // declined: 1 = the key range needs the wide records (the host retries with them)
-  CI_FITS = 17,    // the key range fits the compact records (a wide push tells the host)
-  CI_KBASE = 18,   // the key base of this push's records (the scatters)
-  CI_KSHIFT = 19,  // kmin - kbase: the refines rebase the records to the key minimum
-  CI_KFAIL = 20,   // some key fell outside the records' key field above kbase (the scatters)
-  CI_N = 24
-};
-
 __device__ __forceinline__ int bits_of(uint64_t v) { return v ? 64 - __clzll((long long)v) : 0; }
 
 // A c1info word another kernel produced (atomics / stores of the scatters, stores of
@@ -637,7 +611,7 @@ __global__ __launch_bounds__(1024) void k_c1_check(
   *stream_time = gmx > st0 ? gmx : st0;
   res[0] = none ? INT64_MAX : lo;
   res[1] = none ? INT64_MIN : hi;
-  ctr[0] = ctr[1] = ctr[2] = 0ULL;
+  ctr[CTR_ADDED] = ctr[CTR_FAILED] = ctr[CTR_NEED] = 0ULL;
   if (closed_ctr) *closed_ctr = closed_n;
 }
 
@@ -814,7 +788,6 @@ __device__ __forceinline__ int c1_find_id(const KLDS ID* ids, ID id, uint32_t e,
 // the same source region, which keeps the rows until the partition commits).  Later passes only
 // skip closed rows: not counted, no slots, no HAVING count.
 constexpr unsigned long long C1_NOSLOT = ~0ULL;
-constexpr unsigned long long C1_FATAL = 1ULL << 63;  // in `need`: a reservation past the closed store's capacity
 // n slots of the closed store (an item's thread 0).  The host sizes the store for every live row,
 // so a reservation that ends past the capacity is a bug: it gets no slots (nothing is written)
 // and the push fails (fail bit 4, C1_FATAL in need).
@@ -2593,37 +2566,62 @@ static size_t c1v_layout(khip_agg* a, int log2H, int idw, int log2B, C1VQ* q) {
   return off;
 }
 
-// Returns KHIP_OK with *declined = true when k_c1_check declined the push (nothing persistent was
-// touched: the caller runs the general path on the same batch).
-// cols != nullptr: the value pipeline over argument column vcol (c1v_eligible).
-khip_status c1_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t* ts, const uint8_t* kv,
-                    const uint8_t* rv, int64_t* tot, bool* declined, const int64_t* st_at, bool* retry_wide,
-                    const ColPtrs* cols, int vcol, const RowsIn* rows) {
+constexpr int C1V_UV = 4;  // value scatter: records per thread per step
+
+// One attempt's geometry and scratch pointers (c1_prepare), handed to every stage.
+struct C1Geo {
+  bool val, panes, wide;  // value pipeline; its HOPPING panes; wide records (COUNT(*) only)
+  int P, CH, fbits, log2B, B, F;
+  int64_t n, nT, S, nSt, nchunk_max;  // records, tiles, scatter step (records), steps, refine chunks at most
+  size_t seg_bytes;
+  int64_t* ci;
+  int* cstart;
+  uint16_t* seg;
+  uint32_t *srecAT, *srecT;  // the WIDE records' ts words (12 B/record in all)
+  uint32_t *rc, *rp;
+  uint16_t* ro;
+  int64_t adv, close0;
+  FastDiv fd;
+};
+
+// The merges' parameters and table sizes.
+struct C1Merge {
+  C1Q cq;
+  C1VQ vq0;
+  int log2H, v_log2H;
+  int v_pm;   // the plane mask when a specialised value merge exists for it
+  int v_wpc;  // value merge workgroups per CU
+};
+
+// What follows an attempt k_c1_check declined.
+enum C1Next { C1_DONE, C1_DECLINED, C1_AGAIN_KBASE, C1_AGAIN_WIDE };
+
+// Geometry, scratch sizing and the c1info block's first initialisation.
+static khip_status c1_prepare(khip_agg* a, int64_t n, const C1In& in, C1Geo* g) {
   PartState& s = a->part;
-  *declined = false;
-  *retry_wide = false;
-  const bool val = cols != nullptr || rows != nullptr;
-  const bool panes = val && a->desc.window_kind == KHIP_WINDOW_HOPPING;
-  const int pbits = panes ? 1 : 0;
-  const int CH = val ? C1V_CH : C1_CH;
-  constexpr int UV = 4;  // value scatter: records per thread per step
-  const int P = (int)s.P;
-  const int fbits = s.log2P - s.log2P / 2;
-  const int log2B = s.log2P - fbits;
-  const int B = 1 << log2B, F = 1 << fbits;
-  const int64_t nT = ceil_div(n, C1_TILE);
-  const int64_t S = val ? (int64_t)UV * C1_NT : (int64_t)8 * C1_NT;  // scatter step (records)
-  const int64_t nSt = nT * (C1_TILE / S);                             // steps (runs per bucket)
-  const int64_t nchunk_max = ceil_div(n, CH) + B;
+  g->val = in.cols != nullptr || in.rows != nullptr;
+  g->panes = g->val && a->desc.window_kind == KHIP_WINDOW_HOPPING;
+  g->CH = g->val ? C1V_CH : C1_CH;
+  g->P = (int)s.P;
+  g->fbits = s.log2P - s.log2P / 2;
+  g->log2B = s.log2P - g->fbits;
+  g->B = 1 << g->log2B;
+  g->F = 1 << g->fbits;
+  g->n = n;
+  g->nT = ceil_div(n, C1_TILE);
+  g->S = g->val ? (int64_t)C1V_UV * C1_NT : (int64_t)8 * C1_NT;
+  g->nSt = g->nT * (C1_TILE / g->S);  // (runs per bucket)
+  g->nchunk_max = ceil_div(n, g->CH) + g->B;
+  const int64_t B = g->B, nSt = g->nSt, nT = g->nT;
   KHIP_TRY(s.c1rc.ensure((size_t)B * nSt * 4));
   KHIP_TRY(s.c1rp.ensure(((size_t)B * nSt + 1) * 4));
   KHIP_TRY(s.c1ro.ensure((size_t)B * nSt * 2));
   KHIP_TRY(s.c1bb.ensure((size_t)(B + 1) * 8));
-  const size_t seg_bytes = ((size_t)nchunk_max * (F + 1) * 2 + 255) & ~(size_t)255;  // cstart 256-B aligned
-  KHIP_TRY(s.c1seg.ensure(seg_bytes + (size_t)(B + 1) * 4));
+  g->seg_bytes = ((size_t)g->nchunk_max * (g->F + 1) * 2 + 255) & ~(size_t)255;  // cstart 256-B aligned
+  KHIP_TRY(s.c1seg.ensure(g->seg_bytes + (size_t)(B + 1) * 4));
   KHIP_TRY(s.tilemax.ensure(nT * 32));  // per tile: stream-time max, smallest ts, late bound, ok
   KHIP_TRY(s.tpart.ensure(nT * 8 * T_NPART));
-  KHIP_TRY(s.prn.ensure((size_t)P * 4));
+  KHIP_TRY(s.prn.ensure((size_t)g->P * 4));
   KHIP_TRY(s.res.ensure(16));
   KHIP_TRY(s.closed_ctr.ensure(8));
   if (s.scat_cap < n) {
@@ -2639,108 +2637,121 @@ khip_status c1_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t* 
     init[CI_KMAX] = INT64_MIN;
     KHIP_TRY_HIP(hipMemcpy(s.c1info.p, init, sizeof(init), hipMemcpyHostToDevice));
   }
-  int64_t* ci = s.c1info.as<int64_t>();
+  g->ci = s.c1info.as<int64_t>();
 #ifdef KHIP_TUNING
   {
     const int64_t dbg = knob("KHIP_C1_DEBUG", 0);
-    KHIP_TRY_HIP(hipMemcpyAsync(ci + CI_N - 1, &dbg, 8, hipMemcpyHostToDevice, a->stream));
+    KHIP_TRY_HIP(hipMemcpyAsync(g->ci + CI_N - 1, &dbg, 8, hipMemcpyHostToDevice, a->stream));
     KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
   }
 #endif
-  int* cstart = (int*)(s.c1seg.as<char>() + seg_bytes);
-  uint16_t* seg = s.c1seg.as<uint16_t>();
-  const int64_t adv = a->desc.advance_ms;
-  const FastDiv fd = make_fastdiv(adv);
-  const int64_t close0 = a->host_stream_time >= 0 ? a->host_stream_time - a->grace : INT64_MIN;
-  if (s.closed_cap < s.closed_n + (a->occ - s.closed_n)) {  // worst case every live row closes in this push
-    const int64_t live = a->occ - s.closed_n;
-    const int64_t ncap = next_pow2(std::max<int64_t>(1024, s.closed_n + live));
-    DevBuf nc;
-    KHIP_TRY(nc.ensure((size_t)ncap * a->sw * 8));
-    if (s.closed_n)
-      KHIP_TRY_HIP(hipMemcpyAsync(nc.p, s.closed.p, (size_t)s.closed_n * a->sw * 8, hipMemcpyDeviceToDevice, a->stream));
-    KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
-    s.closed.release();
-    s.closed = std::move(nc);
-    nc.p = nullptr;
-    s.closed_cap = ncap;
-  }
+  g->cstart = (int*)(s.c1seg.as<char>() + g->seg_bytes);
+  g->seg = s.c1seg.as<uint16_t>();
+  g->adv = a->desc.advance_ms;
+  g->fd = make_fastdiv(g->adv);
+  g->close0 = a->host_stream_time >= 0 ? a->host_stream_time - a->grace : INT64_MIN;
   // wide records (key hash + u32 ts words) when the key range did not fit 32 bits last time: the
   // host predicts the format, k_c1_check declines a compact push whose keys do not fit
-  const bool wide = !val && s.c1_wide;
-  uint32_t* srecAT = (uint32_t*)(s.srecA.as<uint64_t>() + n + 1);  // WIDE ts words (12 B/record in all)
-  uint32_t* srecT = (uint32_t*)(s.srec.as<uint64_t>() + n + 1);
-  uint32_t* rc = s.c1rc.as<uint32_t>();
-  uint32_t* rp = s.c1rp.as<uint32_t>();
-  uint16_t* ro = s.c1ro.as<uint16_t>();
-  const int has_kb = s.c1_kb_valid ? 1 : 0;
-  // 1. records → step runs (the key range, time base and bucket counts in the same read)
+  g->wide = !g->val && s.c1_wide;
+  g->srecAT = (uint32_t*)(s.srecA.as<uint64_t>() + n + 1);
+  g->srecT = (uint32_t*)(s.srec.as<uint64_t>() + n + 1);
+  g->rc = s.c1rc.as<uint32_t>();
+  g->rp = s.c1rp.as<uint32_t>();
+  g->ro = s.c1ro.as<uint16_t>();
+  return KHIP_OK;
+}
+
+// 1. records → step runs (the key range, time base and bucket counts in the same read)
+// 2. each (bucket, step) run's place in its bucket's order; the bucket bases
+static khip_status c1_scatter(khip_agg* a, const C1In& in, const C1Geo& g) {
+  PartState& s = a->part;
   ev_record_part(a, 0);
-  if (val) {
-    const C1VCol vc{rows ? nullptr : cols->data[vcol], rows ? nullptr : cols->valid[vcol], a->ap.col_type[vcol]};
+  const int has_kb = s.c1_kb_valid ? 1 : 0;
+  const int64_t* st_at = in.st_at;
+  if (g.val) {
+    constexpr int UV = C1V_UV;
+    const RowsIn* rows = in.rows;
+    const C1VCol vc{rows ? nullptr : in.cols->data[in.vcol], rows ? nullptr : in.cols->valid[in.vcol],
+                    a->ap.col_type[in.vcol]};
     const RowsIn ri = rows ? *rows : RowsIn{};
     auto sk = rows ? (st_at ? k_c1v_scatter<UV, C1_NT, true, true> : k_c1v_scatter<UV, C1_NT, false, true>)
                    : (st_at ? k_c1v_scatter<UV, C1_NT, true, false> : k_c1v_scatter<UV, C1_NT, false, false>);
-    const size_t lds = run_stage_lds(B, UV * C1_NT, 16, false) + run_cnt_lds(B, C1_TILE / (UV * C1_NT));
+    const size_t lds = run_stage_lds(g.B, UV * C1_NT, 16, false) + run_cnt_lds(g.B, C1_TILE / (UV * C1_NT));
     if (lds > 64 * 1024) hipFuncSetAttribute((const void*)sk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(sk, dim3(nT), dim3(C1_NT), lds, a->stream, keys, ts, kv, rv, vc, ri, n, nT, log2B, rc, ro, nSt,
-                       (ulonglong2*)s.srecA.p, s.tilemax.as<int64_t>(), s.tpart.as<int64_t>(), ci, st_at,
-                       a->desc.size_ms, adv, fd, a->desc.size_ms != adv ? 1 : 0, a->grace,
-                       (const int64_t*)a->stream_time.as<int64_t>(), s.c1_kbase, has_kb);
-    KHIP_TRY_HIP(hipGetLastError());
+    hipLaunchKernelGGL(sk, dim3(g.nT), dim3(C1_NT), lds, a->stream, in.keys, in.ts, in.kv, in.rv, vc, ri, g.n, g.nT,
+                       g.log2B, g.rc, g.ro, g.nSt, (ulonglong2*)s.srecA.p, s.tilemax.as<int64_t>(),
+                       s.tpart.as<int64_t>(), g.ci, st_at, a->desc.size_ms, g.adv, g.fd,
+                       a->desc.size_ms != g.adv ? 1 : 0, a->grace, (const int64_t*)a->stream_time.as<int64_t>(),
+                       s.c1_kbase, has_kb);
   } else {
     constexpr int U = 8;
-    auto sk = wide ? (st_at ? k_c1_scatter<U, C1_NT, true, true> : k_c1_scatter<U, C1_NT, true, false>)
-                   : (st_at ? k_c1_scatter<U, C1_NT, false, true> : k_c1_scatter<U, C1_NT, false, false>);
-    const size_t lds = run_stage_lds(B, U * C1_NT, 8, wide) + run_cnt_lds(B, C1_TILE / (U * C1_NT));
+    auto sk = g.wide ? (st_at ? k_c1_scatter<U, C1_NT, true, true> : k_c1_scatter<U, C1_NT, true, false>)
+                     : (st_at ? k_c1_scatter<U, C1_NT, false, true> : k_c1_scatter<U, C1_NT, false, false>);
+    const size_t lds = run_stage_lds(g.B, U * C1_NT, 8, g.wide) + run_cnt_lds(g.B, C1_TILE / (U * C1_NT));
     if (lds > 64 * 1024) hipFuncSetAttribute((const void*)sk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(sk, dim3(nT), dim3(C1_NT), lds, a->stream, keys, ts, kv, rv, n, nT, log2B, rc, ro, nSt,
-                       s.srecA.as<uint64_t>(), s.tilemax.as<int64_t>(), s.tpart.as<int64_t>(), ci, st_at, srecAT,
-                       a->desc.size_ms, adv, fd, a->grace, (const int64_t*)a->stream_time.as<int64_t>(), s.c1_kbase,
-                       has_kb);
-    KHIP_TRY_HIP(hipGetLastError());
+    hipLaunchKernelGGL(sk, dim3(g.nT), dim3(C1_NT), lds, a->stream, in.keys, in.ts, in.kv, in.rv, g.n, g.nT, g.log2B,
+                       g.rc, g.ro, g.nSt, s.srecA.as<uint64_t>(), s.tilemax.as<int64_t>(), s.tpart.as<int64_t>(), g.ci,
+                       st_at, g.srecAT, a->desc.size_ms, g.adv, g.fd, a->grace,
+                       (const int64_t*)a->stream_time.as<int64_t>(), s.c1_kbase, has_kb);
   }
-  // 2. each (bucket, step) run's place in its bucket's order; the bucket bases
-  KHIP_TRY((ksort::scan_excl<uint32_t, uint32_t>(a->stream, s.c1scan, rc, rp, (int64_t)B * nSt, true, nullptr)));
-  hipLaunchKernelGGL(k_c1_bases, dim3(1), dim3(256), 0, a->stream, (const uint32_t*)rp, nSt, B, s.c1bb.as<int64_t>());
+  KHIP_TRY_HIP(hipGetLastError());
+  KHIP_TRY((ksort::scan_excl<uint32_t, uint32_t>(a->stream, s.c1scan, g.rc, g.rp, (int64_t)g.B * g.nSt, true, nullptr)));
+  hipLaunchKernelGGL(k_c1_bases, dim3(1), dim3(256), 0, a->stream, (const uint32_t*)g.rp, g.nSt, g.B,
+                     s.c1bb.as<int64_t>());
   ev_record_part(a, 1);
-  // 4. accept or decline
-  hipLaunchKernelGGL(k_c1_check, dim3(1), dim3(1024), 0, a->stream, s.tilemax.as<int64_t>(), nT,
-                     a->desc.size_ms, adv, fd, a->grace, close0, s.res_fresh ? 1 : 0, log2B, s.log2P, wide ? 1 : 0,
-                     val ? C1V_CH : C1_CH, val ? 31 : 32, pbits, s.c1bb.as<int64_t>(), cstart, ci,
-                     a->stream_time.as<int64_t>(), s.res.as<int64_t>(),
-                     s.ctr.as<unsigned long long>(), s.closed_ctr.as<unsigned long long>(),
-                     (unsigned long long)s.closed_n);
-  // 5. refine: each chunk's step runs (k_c1_chunks), chunks → partition-sorted, segment table
-  KHIP_TRY(s.c1ci.ensure((size_t)nchunk_max * 8));
-  hipLaunchKernelGGL(k_c1_chunks, dim3((unsigned)ceil_div(nchunk_max, 256)), dim3(256), 0, a->stream, (const int*)cstart, B,
-                     (const int64_t*)s.c1bb.as<int64_t>(), (const uint32_t*)rp, nSt, CH, (const int64_t*)ci,
-                     s.c1ci.as<uint32_t>());
-  if (val) {
+  return KHIP_OK;
+}
+
+// 5b. chunks → partition-sorted records and the segment table
+static khip_status c1_refine(khip_agg* a, const C1Geo& g) {
+  PartState& s = a->part;
+  if (g.val) {
     auto rk = k_c1v_refine<C1V_CH / C1_NT, C1_NT>;
-    const size_t lds = (((size_t)F * 8 + 15) & ~(size_t)15) + (size_t)C1V_CH * 16;
+    const size_t lds = (((size_t)g.F * 8 + 15) & ~(size_t)15) + (size_t)C1V_CH * 16;
     hipFuncSetAttribute((const void*)rk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(rk, dim3((unsigned)nchunk_max), dim3(C1_NT), lds, a->stream, (const ulonglong2*)s.srecA.p,
-                       s.c1bb.as<int64_t>(), cstart, log2B, s.log2P, fbits, (ulonglong2*)s.srec.p, seg, ci,
-                       (const uint32_t*)rp, (const uint16_t*)ro, nSt, S, (const uint32_t*)s.c1ci.as<uint32_t>());
-    KHIP_TRY_HIP(hipGetLastError());
+    hipLaunchKernelGGL(rk, dim3((unsigned)g.nchunk_max), dim3(C1_NT), lds, a->stream, (const ulonglong2*)s.srecA.p,
+                       s.c1bb.as<int64_t>(), g.cstart, g.log2B, s.log2P, g.fbits, (ulonglong2*)s.srec.p, g.seg, g.ci,
+                       (const uint32_t*)g.rp, (const uint16_t*)g.ro, g.nSt, g.S,
+                       (const uint32_t*)s.c1ci.as<uint32_t>());
   } else {
     constexpr int U = C1_CH / C1_NT;
-    auto rk = wide ? k_c1_refine<U, C1_NT, true> : k_c1_refine<U, C1_NT, false>;
-    const size_t lds = (size_t)F * 8 + (size_t)C1_CH * 8;
+    auto rk = g.wide ? k_c1_refine<U, C1_NT, true> : k_c1_refine<U, C1_NT, false>;
+    const size_t lds = (size_t)g.F * 8 + (size_t)C1_CH * 8;
     if (lds > 64 * 1024) hipFuncSetAttribute((const void*)rk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(rk, dim3((unsigned)nchunk_max), dim3(C1_NT), lds, a->stream,
-                       s.srecA.as<uint64_t>(), s.c1bb.as<int64_t>(), cstart, log2B, s.log2P, fbits,
-                       s.srec.as<uint64_t>(), seg, ci, (const uint32_t*)srecAT, srecT, (const uint32_t*)rp,
-                       (const uint16_t*)ro, nSt, S, (const uint32_t*)s.c1ci.as<uint32_t>());
-    KHIP_TRY_HIP(hipGetLastError());
+    hipLaunchKernelGGL(rk, dim3((unsigned)g.nchunk_max), dim3(C1_NT), lds, a->stream, s.srecA.as<uint64_t>(),
+                       s.c1bb.as<int64_t>(), g.cstart, g.log2B, s.log2P, g.fbits, s.srec.as<uint64_t>(), g.seg, g.ci,
+                       (const uint32_t*)g.srecAT, g.srecT, (const uint32_t*)g.rp, (const uint16_t*)g.ro, g.nSt, g.S,
+                       (const uint32_t*)s.c1ci.as<uint32_t>());
   }
+  KHIP_TRY_HIP(hipGetLastError());
+  return KHIP_OK;
+}
+
+// The record stages: scatter, scan, bases, check, chunks, refine.
+static khip_status c1_records(khip_agg* a, const C1In& in, const C1Geo& g) {
+  PartState& s = a->part;
+  KHIP_TRY(c1_scatter(a, in, g));
+  // 4. accept or decline
+  hipLaunchKernelGGL(k_c1_check, dim3(1), dim3(1024), 0, a->stream, s.tilemax.as<int64_t>(), g.nT, a->desc.size_ms,
+                     g.adv, g.fd, a->grace, g.close0, s.res_fresh ? 1 : 0, g.log2B, s.log2P, g.wide ? 1 : 0, g.CH,
+                     g.val ? 31 : 32, g.panes ? 1 : 0, s.c1bb.as<int64_t>(), g.cstart, g.ci,
+                     a->stream_time.as<int64_t>(), s.res.as<int64_t>(), s.ctr.as<unsigned long long>(),
+                     s.closed_ctr.as<unsigned long long>(), (unsigned long long)s.closed_n);
+  // 5. refine: each chunk's step runs (k_c1_chunks), chunks → partition-sorted, segment table
+  KHIP_TRY(s.c1ci.ensure((size_t)g.nchunk_max * 8));
+  hipLaunchKernelGGL(k_c1_chunks, dim3((unsigned)ceil_div(g.nchunk_max, 256)), dim3(256), 0, a->stream,
+                     (const int*)g.cstart, g.B, (const int64_t*)s.c1bb.as<int64_t>(), (const uint32_t*)g.rp, g.nSt, g.CH,
+                     (const int64_t*)g.ci, s.c1ci.as<uint32_t>());
+  KHIP_TRY(c1_refine(a, g));
   ev_record_part(a, 2);
-  // 6. merge partitions (+ retries), as part_push's pass loop
-  const int log2H = (int)knob("KHIP_C1_LOG2H", 12);
+  return KHIP_OK;
+}
+
+// The COUNT(*) merge's parameters.
+static C1Q c1_make_q(khip_agg* a, const C1Geo& g, int log2H) {
   C1Q cq{};
-  cq.log2P = s.log2P;
-  cq.fbits = fbits;
+  cq.log2P = a->part.log2P;
+  cq.fbits = g.fbits;
   cq.log2H = log2H;
   cq.sw = a->sw;
   cq.hv_active = a->having.active;
@@ -2748,261 +2759,270 @@ khip_status c1_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t* 
   cq.hv_i64 = a->having.i64;
   cq.hmax = (int)((int64_t)(1 << log2H) * 3 / 4);
   cq.size = a->desc.size_ms;
-  cq.adv = adv;
-  cq.fd = fd;
-  cq.fd32 = make_fastdiv32((uint32_t)adv);
-  // the value pipeline's merge: the largest table (up to 2^12 entries) whose LDS lets two
-  // workgroups share a CU
-  C1VQ vq0{};
-  int v_log2H = 12;
-  int v_pm = 0;  // the plane mask when a specialised merge exists for it
-  const int v_wpc = (int)knob("KHIP_C1V_WG_PER_CU", 2);  // merge workgroups per CU
-  if (val) {
-    // sized for 32-bit identities (the common case); 64-bit ones (a key range past 31 - window
-    // bits) run at one workgroup per CU when their table does not fit two
-    while (v_log2H > 9 && c1v_layout(a, v_log2H, 4, log2B, &vq0) > C1V_LDS2) v_log2H--;
-    v_log2H = (int)knob("KHIP_C1V_LOG2H", v_log2H);
+  cq.adv = g.adv;
+  cq.fd = g.fd;
+  cq.fd32 = make_fastdiv32((uint32_t)g.adv);
+  return cq;
+}
 
-    vq0.log2P = s.log2P;
-    vq0.fbits = fbits;
-    vq0.log2H = v_log2H;
-    vq0.sw = a->sw;
-    vq0.hmax = (int)((int64_t)(1 << v_log2H) * 3 / 4);
-    vq0.fan = (int)(a->desc.size_ms / adv);
-    vq0.f64 = 0;
-    for (int k = 0; k < C1V_MAXW; k++) {
-      vq0.word_op[k] = -1;
-      vq0.init[k] = (uint64_t)a->init.w[k];
-    }
-    for (int o = 0; o < a->ap.n_ops; o++) {
-      vq0.word_op[a->ap.ops[o].word] = a->ap.ops[o].kind;
-      if (a->ap.ops[o].kind == OP_ADD_F64) vq0.f64 = 1;
-    }
-    if (a->ap.col_type[vcol] == KHIP_TYPE_DOUBLE) vq0.f64 = 1;
-    for (int o = 0; o < a->ap.n_ops; o++) {
-      const int k = a->ap.ops[o].kind;
-      v_pm |= k == OP_INC ? PM_STAR : k == OP_INC_VALID ? PM_CNT : k == OP_MIN ? PM_MIN : k == OP_MAX ? PM_MAX : PM_SUM;
-    }
-    v_pm |= PM_SPEC | (vq0.f64 ? PM_F64 : 0);
-    if ((v_pm != PM_C5 && v_pm != PM_C3) || knob("KHIP_C1V_SPEC", 1) == 0) v_pm = 0;
-    vq0.size = a->desc.size_ms;
-    vq0.adv = adv;
-    vq0.fd = fd;
-    vq0.fd32 = make_fastdiv32((uint32_t)adv);
-    vq0.having = a->having;
+// The value merge's parameters: the largest table (up to 2^12 entries) whose LDS lets two
+// workgroups share a CU, and the plane mask when a specialised merge exists for it.
+static void c1v_make_q(khip_agg* a, const C1Geo& g, int vcol, C1Merge* m) {
+  C1VQ& vq0 = m->vq0;
+  // sized for 32-bit identities (the common case); 64-bit ones (a key range past 31 - window
+  // bits) run at one workgroup per CU when their table does not fit two
+  m->v_log2H = 12;
+  while (m->v_log2H > 9 && c1v_layout(a, m->v_log2H, 4, g.log2B, &vq0) > C1V_LDS2) m->v_log2H--;
+  m->v_log2H = (int)knob("KHIP_C1V_LOG2H", m->v_log2H);
+
+  vq0.log2P = a->part.log2P;
+  vq0.fbits = g.fbits;
+  vq0.log2H = m->v_log2H;
+  vq0.sw = a->sw;
+  vq0.hmax = (int)((int64_t)(1 << m->v_log2H) * 3 / 4);
+  vq0.fan = (int)(a->desc.size_ms / g.adv);
+  vq0.f64 = 0;
+  for (int k = 0; k < C1V_MAXW; k++) {
+    vq0.word_op[k] = -1;
+    vq0.init[k] = (uint64_t)a->init.w[k];
   }
-  int64_t added_total = 0;
-  // sub-passes per partition: the pipeline's own LDS table (hmax), not the general merge's — a
-  // partition starts with enough of them for the hinted groups, and keeps those a push needed
-  {
-    const int64_t hm = val ? vq0.hmax : cq.hmax;
-    if ((int64_t)s.c1psbits.size() != P || s.c1ps_hmax != hm) {
-      int s0 = 0;
-      while (s0 < 12 && s.hint_groups / P > (hm * 7 / 10) << s0) s0++;
-      s.c1psbits.assign(P, (uint8_t)s0);
-      s.c1ps_hmax = hm;
-    }
+  for (int o = 0; o < a->ap.n_ops; o++) {
+    vq0.word_op[a->ap.ops[o].word] = a->ap.ops[o].kind;
+    if (a->ap.ops[o].kind == OP_ADD_F64) vq0.f64 = 1;
   }
-  std::vector<int> sbits(s.c1psbits.begin(), s.c1psbits.end());
-  std::vector<uint32_t> plist, work;
-  bool subs0 = false;
-  for (int p = 0; p < P && !subs0; p++) subs0 = sbits[p] > 0;
-  if (subs0) {
-    for (int p = 0; p < P; p++)
-      for (int k = 0; k < (1 << sbits[p]); k++) work.push_back((uint32_t)p | ((uint32_t)sbits[p] << 16) | ((uint32_t)k << 20));
-    KHIP_TRY(s.work.ensure(work.size() * 4));
-    KHIP_TRY_HIP(hipMemcpyAsync(s.work.p, work.data(), work.size() * 4, hipMemcpyHostToDevice, a->stream));
+  if (a->ap.col_type[vcol] == KHIP_TYPE_DOUBLE) vq0.f64 = 1;
+  int pm = 0;
+  for (int o = 0; o < a->ap.n_ops; o++) {
+    const int k = a->ap.ops[o].kind;
+    pm |= k == OP_INC ? PM_STAR : k == OP_INC_VALID ? PM_CNT : k == OP_MIN ? PM_MIN : k == OP_MAX ? PM_MAX : PM_SUM;
   }
-  std::vector<uint8_t> host_fail;
-  const bool probe = knob("KHIP_AGG_PROBE", 0) != 0;
-  DevBuf dbgbuf;
-  if (probe) {
-    KHIP_TRY(dbgbuf.ensure(64));
-    KHIP_TRY_HIP(hipMemsetAsync(dbgbuf.p, 0, 64, a->stream));
-  }
-  for (int pass = 0;; pass++) {
-    unsigned long long* dbg = probe && pass == 0 ? dbgbuf.as<unsigned long long>() : nullptr;
-    cq.cmax = s.cmax;
-    cq.chg = a->changelog ? a->chg.as<uint8_t>() : nullptr;
-    if (pass > 0) KHIP_TRY_HIP(hipMemsetAsync(s.ctr.p, 0, 24, a->stream));
-    const uint32_t* wk = (pass == 0 && !subs0) ? nullptr : s.work.as<uint32_t>();
-    const int64_t nwork = (pass == 0 && !subs0) ? P : (int64_t)work.size();
-    const int64_t grid = std::min<int64_t>(nwork, (int64_t)s.n_cu * knob("KHIP_MERGE_WG_PER_CU", 2));
-    // compact records: both identity widths are launched, the one k_c1_check did not choose exits
-    // at once; wide records: 64-bit identities
-    for (int idw = wide ? 1 : 0; idw < 2 && val; idw++) {
-      C1VQ vq = vq0;
-      const size_t lds = c1v_layout(a, v_log2H, idw == 0 ? 4 : 8, log2B, &vq);
-      vq.cmax = s.cmax;
-      vq.chg = a->changelog ? a->chg.as<uint8_t>() : nullptr;
-      // the benchmarks' plane shapes have instantiations of their own (PM_C5, PM_C3), every other
-      // one reads the planes from the parameters; AU 2 at <= 128 VGPRs (two workgroups per CU)
-      auto pick = [&](auto pmc) {
-        constexpr int PMv = decltype(pmc)::value;
-        return panes ? (idw == 0 ? k_c1v_merge<512, 2, uint32_t, true, 4, PMv> : k_c1v_merge<512, 2, uint64_t, true, 4, PMv>)
+  pm |= PM_SPEC | (vq0.f64 ? PM_F64 : 0);
+  m->v_pm = ((pm != PM_C5 && pm != PM_C3) || knob("KHIP_C1V_SPEC", 1) == 0) ? 0 : pm;
+  vq0.size = a->desc.size_ms;
+  vq0.adv = g.adv;
+  vq0.fd = g.fd;
+  vq0.fd32 = make_fastdiv32((uint32_t)g.adv);
+  vq0.having = a->having;
+}
+
+// One pass's merge over the nwork items of wk (null: one per partition).  Compact records: both
+// identity widths are launched, the one k_c1_check did not choose exits at once; wide records:
+// 64-bit identities.
+static khip_status c1_launch_merge(khip_agg* a, const C1Geo& g, const C1Merge& m, int pass, const uint32_t* wk,
+                                   int64_t nwork, unsigned long long* dbg) {
+  PartState& s = a->part;
+  unsigned long long* ctr = s.ctr.as<unsigned long long>();
+  uint8_t* chg = a->changelog ? a->chg.as<uint8_t>() : nullptr;  // (a retry's regrow moves it)
+  for (int idw = g.wide ? 1 : 0; idw < 2 && g.val; idw++) {
+    C1VQ vq = m.vq0;
+    const size_t lds = c1v_layout(a, m.v_log2H, idw == 0 ? 4 : 8, g.log2B, &vq);
+    vq.cmax = s.cmax;
+    vq.chg = chg;
+    // the benchmarks' plane shapes have instantiations of their own (PM_C5, PM_C3), every other
+    // one reads the planes from the parameters; AU 2 at <= 128 VGPRs (two workgroups per CU)
+    auto pick = [&](auto pmc) {
+      constexpr int PMv = decltype(pmc)::value;
+      return g.panes ? (idw == 0 ? k_c1v_merge<512, 2, uint32_t, true, 4, PMv> : k_c1v_merge<512, 2, uint64_t, true, 4, PMv>)
                      : (idw == 0 ? k_c1v_merge<512, 2, uint32_t, false, 4, PMv> : k_c1v_merge<512, 2, uint64_t, false, 4, PMv>);
-      };
-      auto mk = v_pm == PM_C5 ? pick(std::integral_constant<int, PM_C5>{})
-                              : (v_pm == PM_C3 ? pick(std::integral_constant<int, PM_C3>{}) : pick(std::integral_constant<int, 0>{}));
-      hipFuncSetAttribute((const void*)mk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      KHIP_TRY(s.c1vq.ensure(sizeof(C1VQ)));
-      KHIP_TRY(s.c1vq_h.ensure(2 * sizeof(C1VQ)));
-      C1VQ* hq = (C1VQ*)s.c1vq_h.p + idw;
-      *hq = vq;
-      KHIP_TRY_HIP(hipMemcpyAsync(s.c1vq.p, hq, sizeof(C1VQ), hipMemcpyHostToDevice, a->stream));
-      const int64_t vgrid = std::min<int64_t>(nwork, (int64_t)s.n_cu * (lds <= C1V_LDS2 ? v_wpc : 1));
-      hipLaunchKernelGGL(mk, dim3(vgrid), dim3(512), lds, a->stream, s.c1vq.as<C1VQ>(), wk, nwork, s.c1bb.as<int64_t>(), cstart, seg,
-                         (const ulonglong2*)s.srec.p, pass == 0 ? 1 : 0, s.buf[0].as<uint64_t>(), s.buf[1].as<uint64_t>(),
-                         s.sel.as<uint8_t>(), s.cnt.as<int64_t>(), s.newcnt.as<unsigned long long>(),
-                         s.fail.as<uint8_t>(), s.ctr.as<unsigned long long>() + 2, close0, s.closed.as<uint64_t>(),
-                         s.closed_ctr.as<unsigned long long>(), (unsigned long long)s.closed_cap, ci,
-                         s.hnew.as<unsigned long long>(), s.ctr.as<unsigned long long>() + 12, s.prn.as<uint32_t>(), dbg);
-    }
-    for (int idw = wide ? 1 : 0; idw < 2 && !val; idw++) {
-      auto mk = wide ? k_c1_merge<512, 3, uint64_t, true>
+    };
+    auto mk = m.v_pm == PM_C5 ? pick(std::integral_constant<int, PM_C5>{})
+                              : (m.v_pm == PM_C3 ? pick(std::integral_constant<int, PM_C3>{}) : pick(std::integral_constant<int, 0>{}));
+    hipFuncSetAttribute((const void*)mk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    KHIP_TRY(s.c1vq.ensure(sizeof(C1VQ)));
+    KHIP_TRY(s.c1vq_h.ensure(2 * sizeof(C1VQ)));
+    C1VQ* hq = (C1VQ*)s.c1vq_h.p + idw;
+    *hq = vq;
+    KHIP_TRY_HIP(hipMemcpyAsync(s.c1vq.p, hq, sizeof(C1VQ), hipMemcpyHostToDevice, a->stream));
+    const int64_t vgrid = std::min<int64_t>(nwork, (int64_t)s.n_cu * (lds <= C1V_LDS2 ? m.v_wpc : 1));
+    hipLaunchKernelGGL(mk, dim3(vgrid), dim3(512), lds, a->stream, s.c1vq.as<C1VQ>(), wk, nwork, s.c1bb.as<int64_t>(),
+                       g.cstart, g.seg, (const ulonglong2*)s.srec.p, pass == 0 ? 1 : 0, s.buf[0].as<uint64_t>(),
+                       s.buf[1].as<uint64_t>(), s.sel.as<uint8_t>(), s.cnt.as<int64_t>(),
+                       s.newcnt.as<unsigned long long>(), s.fail.as<uint8_t>(), ctr + CTR_NEED, g.close0,
+                       s.closed.as<uint64_t>(), s.closed_ctr.as<unsigned long long>(),
+                       (unsigned long long)s.closed_cap, g.ci, s.hnew.as<unsigned long long>(), ctr + CTR_HAVING_CLOSED,
+                       s.prn.as<uint32_t>(), dbg);
+  }
+  C1Q cq = m.cq;
+  cq.cmax = s.cmax;
+  cq.chg = chg;
+  const int64_t grid = std::min<int64_t>(nwork, (int64_t)s.n_cu * knob("KHIP_MERGE_WG_PER_CU", 2));
+  for (int idw = g.wide ? 1 : 0; idw < 2 && !g.val; idw++) {
+    auto mk = g.wide ? k_c1_merge<512, 3, uint64_t, true>
                      : (idw == 0 ? k_c1_merge<512, 4, uint32_t, false> : k_c1_merge<512, 4, uint64_t, false>);
-      const size_t lds = c1_merge_lds(log2H, idw == 0 ? 4 : 8, log2B);
-      hipFuncSetAttribute((const void*)mk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(mk, dim3(grid), dim3(512), lds, a->stream, cq, wk, nwork, s.c1bb.as<int64_t>(), cstart, seg,
-                         s.srec.as<uint64_t>(), pass == 0 ? 1 : 0, s.buf[0].as<uint64_t>(), s.buf[1].as<uint64_t>(),
-                         s.sel.as<uint8_t>(), s.cnt.as<int64_t>(), s.newcnt.as<unsigned long long>(),
-                         s.fail.as<uint8_t>(), s.ctr.as<unsigned long long>() + 2, close0, s.closed.as<uint64_t>(),
-                         s.closed_ctr.as<unsigned long long>(), (unsigned long long)s.closed_cap, ci,
-                         s.hnew.as<unsigned long long>(), s.ctr.as<unsigned long long>() + 12, s.prn.as<uint32_t>(),
-                         (const uint32_t*)srecT, dbg);
-    }
-    KHIP_TRY_HIP(hipGetLastError());
-    const int nl = pass == 0 ? P : (int)plist.size();
-    hipLaunchKernelGGL(k_part_commit, dim3(ceil_div(std::max(nl, 1), 256)), dim3(256), 0, a->stream,
-                       pass == 0 ? (const int64_t*)ci : (const int64_t*)nullptr, P, s.pbase.as<int64_t>(),
-                       s.prn.as<uint32_t>(), pass == 0 ? nullptr : s.work.as<uint32_t>() + work.size(), nl,
+    const size_t lds = c1_merge_lds(m.log2H, idw == 0 ? 4 : 8, g.log2B);
+    hipFuncSetAttribute((const void*)mk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(mk, dim3(grid), dim3(512), lds, a->stream, cq, wk, nwork, s.c1bb.as<int64_t>(), g.cstart, g.seg,
+                       s.srec.as<uint64_t>(), pass == 0 ? 1 : 0, s.buf[0].as<uint64_t>(), s.buf[1].as<uint64_t>(),
                        s.sel.as<uint8_t>(), s.cnt.as<int64_t>(), s.newcnt.as<unsigned long long>(),
-                       s.fail.as<uint8_t>(), s.ctr.as<unsigned long long>(), s.hcnt.as<unsigned long long>(),
-                       s.hnew.as<unsigned long long>());
-    KHIP_TRY_HIP(hipGetLastError());
-    if (pass == 0) {
-      ev_record_part(a, 3);
-      hipLaunchKernelGGL(k_part_stats, dim3(1), dim3(256), 0, a->stream, s.tpart.as<int64_t>(), nT,
-                         s.closed_ctr.as<unsigned long long>(), a->stream_time.as<int64_t>(),
-                         s.ctr.as<unsigned long long>());
-      KHIP_TRY_HIP(hipMemcpyAsync(s.pinfo.as<int64_t>() + 32, ci, CI_N * 8, hipMemcpyDeviceToHost, a->stream));
-    }
-    unsigned long long* c2 = s.pinfo.as<unsigned long long>() + 8;
-    KHIP_TRY_HIP(hipMemcpyAsync(c2, s.ctr.p, 13 * 8, hipMemcpyDeviceToHost, a->stream));
-    // the closed store's rows after this pass (closed rows leave in the pass that writes their
-    // item): read with the counters, no second round trip
-    KHIP_TRY_HIP(hipMemcpyAsync(s.pinfo.as<unsigned long long>() + 58, s.closed_ctr.p, 8, hipMemcpyDeviceToHost,
-                                a->stream));
+                       s.fail.as<uint8_t>(), ctr + CTR_NEED, g.close0, s.closed.as<uint64_t>(),
+                       s.closed_ctr.as<unsigned long long>(), (unsigned long long)s.closed_cap, g.ci,
+                       s.hnew.as<unsigned long long>(), ctr + CTR_HAVING_CLOSED, s.prn.as<uint32_t>(),
+                       (const uint32_t*)g.srecT, dbg);
+  }
+  KHIP_TRY_HIP(hipGetLastError());
+  return KHIP_OK;
+}
+
+// A declined attempt (hci: the c1info copy; nothing persistent was written): decline the push, or
+// run it again with the keys' true base (once per record format) or with the wide records.
+static khip_status c1_declined_next(khip_agg* a, const C1In& in, const C1Geo& g, bool kretried, C1Next* next) {
+  PartState& s = a->part;
+  const int64_t* hci = s.info()->c1info;
+  bool go_wide = !g.val && hci[CI_REASON] == 1;  // only the record format was wrong
+  if (hci[CI_REASON] == 2 && !kretried) {  // a key outside the field above kb: the true range
+    long long kr[2] = {INT64_MIN, INT64_MIN};
+    KHIP_TRY(s.c1scan.ensure(16));
+    KHIP_TRY_HIP(hipMemcpyAsync(s.c1scan.p, kr, 16, hipMemcpyHostToDevice, a->stream));
+    hipLaunchKernelGGL(k_c1_krange, dim3((unsigned)std::min<int64_t>(ceil_div(g.n, 256), 2048)), dim3(256), 0,
+                       a->stream, in.rows ? (const int64_t*)in.rows->rows : in.keys,
+                       in.rows ? (int64_t)in.rows->rw : 1, g.n, s.c1scan.as<long long>());
+    KHIP_TRY_HIP(hipMemcpyAsync(kr, s.c1scan.p, 16, hipMemcpyDeviceToHost, a->stream));
     KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
-    const int64_t* hci = s.pinfo.as<int64_t>() + 32;
-    if (pass == 0 && hci[CI_GATE] == 0) {  // declined: nothing was written
-      if (hci[CI_REASON] == 2 && !s.c1_kretry) {  // a key outside the field above kb: the true range
-        long long kr[2] = {INT64_MIN, INT64_MIN};
-        KHIP_TRY(s.c1scan.ensure(16));
-        KHIP_TRY_HIP(hipMemcpyAsync(s.c1scan.p, kr, 16, hipMemcpyHostToDevice, a->stream));
-        hipLaunchKernelGGL(k_c1_krange, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), 2048)), dim3(256), 0,
-                           a->stream, rows ? (const int64_t*)rows->rows : keys, rows ? (int64_t)rows->rw : 1, n,
-                           s.c1scan.as<long long>());
-        KHIP_TRY_HIP(hipMemcpyAsync(kr, s.c1scan.p, 16, hipMemcpyDeviceToHost, a->stream));
-        KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
-        const int64_t kmin = (int64_t)~(uint64_t)kr[0], kmax = (int64_t)kr[1];
-        if ((uint64_t)kmax - (uint64_t)kmin < (1ULL << (val ? 31 : 32)) - 1) {  // again with kb = kmin
-          s.c1_kbase = kmin;
-          s.c1_kb_valid = true;
-          s.c1_kretry = true;
-          const khip_status r = c1_push(a, n, keys, ts, kv, rv, tot, declined, st_at, retry_wide, cols, vcol, rows);
-          s.c1_kretry = false;
-          return r;
-        }
-        *declined = true;
-        *retry_wide = !val;  // the range itself is past the compact records
-        if (*retry_wide) s.c1_wide = true;
-        return KHIP_OK;
-      }
-      *declined = true;
-      *retry_wide = !val && hci[CI_REASON] == 1;  // only the record format was wrong
-      if (*retry_wide) s.c1_wide = true;
+    const int64_t kmin = (int64_t)~(uint64_t)kr[0], kmax = (int64_t)kr[1];
+    if ((uint64_t)kmax - (uint64_t)kmin < (1ULL << (g.val ? 31 : 32)) - 1) {  // again with kb = kmin
+      s.c1_kbase = kmin;
+      s.c1_kb_valid = true;
+      *next = C1_AGAIN_KBASE;
       return KHIP_OK;
     }
-    if (pass == 0 && wide && ++s.c1_wide_n % 64 == 0) s.c1_wide = false;  // now and then: compact records again?
-    if (pass == 0 && !wide) {  // the next push's key base: this one's minimum, less a margin for keys below it
-      const int64_t km = hci[CI_KMINC], slack = (int64_t)1 << (val ? 26 : 28);
-      s.c1_kbase = km >= INT64_MIN + slack ? km - slack : km;
-      s.c1_kb_valid = true;
-    }
-    if (dbg) {
-      unsigned long long ph[8] = {};
-      if (hipMemcpy(ph, dbgbuf.p, sizeof(ph), hipMemcpyDeviceToHost) == hipSuccess) {
-        const double g = (double)std::min<int64_t>(P, 2 * s.n_cu) * 100.0;  // 100 MHz ticks → us per workgroup
-        fprintf(stderr, "[%s merge probe] per workgroup (us): start+evict %.1f records %.1f fold %.1f "
-                "mark+count+reserve %.1f write %.1f\n", val ? "c1v" : "c1", ph[0] / g, ph[1] / g, ph[2] / g, ph[3] / g,
-                ph[4] / g);
-      }
-    }
-    if (c2[2] & C1_FATAL)  // (cannot happen: the store holds every live row)
-      return fail(KHIP_E_DEVICE, "the closed store's capacity would be exceeded by a merge's closed rows");
-    added_total += (int64_t)c2[0];
-    if (c2[1] != 0) {
-      host_fail.resize(P);
-      KHIP_TRY_HIP(hipMemcpy(host_fail.data(), s.fail.p, P, hipMemcpyDeviceToHost));
-    }
-#ifdef KHIP_TUNING
-    if (knob("KHIP_C1_TRACE", 0) != 0) {  // one line per pass: the tests' witness that a push was retried
-      int64_t nsub = 0, ft = 0, fr = 0;
-      if (wk)
-        for (const uint32_t x : work) nsub += ((x >> 16) & 0xF) != 0;
-      if (c2[1] != 0)
-        for (int p = 0; p < P; p++) ft += (host_fail[p] & 1) != 0, fr += (host_fail[p] & 2) != 0;
-      fprintf(stderr,
-              "[c1 trace] val=%d P=%d cmax=%lld log2H=%d pass=%d items=%lld sub_items=%lld failed=%llu fail_table=%lld "
-              "fail_region=%lld closed_before=%lld closed_after=%llu\n",
-              val ? 1 : 0, P, (long long)cq.cmax, val ? v_log2H : log2H, pass, (long long)nwork, (long long)nsub, c2[1],
-              (long long)ft, (long long)fr, (long long)s.closed_n, s.pinfo.as<unsigned long long>()[58]);
-    }
-#endif
-    if (c2[1] == 0) break;
-    if (pass > 24) return fail(KHIP_E_DEVICE, "partitioned aggregation could not place the batch");
-    KHIP_TRY_HIP(hipMemsetAsync(s.fail.p, 0, P, a->stream));
-    bool grow = false;
-    plist.clear();
-    work.clear();
-    for (int p = 0; p < P; p++) {
-      if (!host_fail[p]) continue;
-      if (host_fail[p] & 1) sbits[p] = sbits[p] + 1;
-      if (host_fail[p] & 2) grow = true;
-      plist.push_back((uint32_t)p);
-      if (sbits[p] > 12) return fail(KHIP_E_DEVICE, "partition needs more than 4096 sub-passes (extreme key skew)");
-      for (int k = 0; k < (1 << sbits[p]); k++) work.push_back((uint32_t)p | ((uint32_t)sbits[p] << 16) | ((uint32_t)k << 20));
-    }
-    if (grow) KHIP_TRY(part_regrow(a, next_pow2(std::max<int64_t>(s.cmax * 2, (int64_t)c2[2] * 5 / 4 + 64))));
-    std::vector<uint32_t> both(work);
-    both.insert(both.end(), plist.begin(), plist.end());
-    KHIP_TRY(s.work.ensure(both.size() * 4));
-    KHIP_TRY_HIP(hipMemcpyAsync(s.work.p, both.data(), both.size() * 4, hipMemcpyHostToDevice, a->stream));
+    go_wide = !g.val;  // the range itself is past the compact records
   }
-  for (int p = 0; p < P; p++) s.c1psbits[p] = (uint8_t)std::max<int>(s.c1psbits[p], sbits[p]);
-  s.res_fresh = false;
-  s.last_c1 = true;
-  {
-    const unsigned long long* hc = s.pinfo.as<unsigned long long>() + 8;
-    s.having_total = (int64_t)(hc[11] + hc[12]);
-  }
-  const unsigned long long* st = s.pinfo.as<unsigned long long>() + 8;
-  // the closed store's rows after every pass (read with the last pass's counters)
-  const int64_t cn = (int64_t)s.pinfo.as<unsigned long long>()[58];
-  added_total += cn - s.closed_n;  // evicted rows left the live regions but are still groups
-  s.closed_n = cn;
-  a->host_stream_time = (int64_t)st[4 + T_NPART];
-  int64_t c[T_NPART];
-  for (int k = 0; k < T_NPART; k++) c[k] = (int64_t)st[3 + k];
-  tot[P_ACCEPTED] += c[T_ACCEPTED];
-  tot[P_NULL_KEY] += c[T_NULL_KEY];
-  tot[P_NULL_ROW] += c[T_NULL_ROW];
-  tot[P_BAD_TS] += c[T_BAD_TS];
-  tot[P_APPLIED] += c[T_APPLIED];
-  tot[P_LATE] += c[T_LATE];
-  tot[P_NEW] += added_total;
+  if (go_wide) s.c1_wide = true;
+  *next = go_wide ? C1_AGAIN_WIDE : C1_DECLINED;
   return KHIP_OK;
+}
+
+// Sub-passes per partition: the pipeline's own LDS table (hmax), not the general merge's — a
+// partition starts with enough of them for the hinted groups, and keeps those a push needed.
+static void c1_start_bits(PartState& s, int64_t hm) {
+  if ((int64_t)s.c1psbits.size() == s.P && s.c1ps_hmax == hm) return;
+  int s0 = 0;
+  while (s0 < RETRY_MAX_SBITS && s.hint_groups / s.P > (hm * 7 / 10) << s0) s0++;
+  s.c1psbits.assign(s.P, (uint8_t)s0);
+  s.c1ps_hmax = hm;
+}
+
+// *declined = true when k_c1_check declined the push (nothing persistent was touched: the caller
+// runs the general path on the same batch).  A declined attempt may be followed by one with the
+// keys' true base, and (COUNT(*)) by one with wide records, which again may change its key base.
+khip_status c1_push(khip_agg* a, int64_t n, const C1In& in, int64_t* tot, bool* declined) {
+  PartState& s = a->part;
+  *declined = false;
+  const bool probe = knob("KHIP_AGG_PROBE", 0) != 0;
+  bool kretried = false, wide_tried = false;
+  for (;;) {  // attempts (at most four)
+    C1Geo g;
+    KHIP_TRY(c1_prepare(a, n, in, &g));
+    KHIP_TRY(part_grow_closed(a));
+    KHIP_TRY(c1_records(a, in, g));
+    // 6. merge partitions (+ retries: DESIGN.md (d))
+    C1Merge m{};
+    m.log2H = (int)knob("KHIP_C1_LOG2H", 12);
+    m.cq = c1_make_q(a, g, m.log2H);
+    m.v_wpc = (int)knob("KHIP_C1V_WG_PER_CU", 2);
+    if (g.val) c1v_make_q(a, g, in.vcol, &m);
+    c1_start_bits(s, g.val ? m.vq0.hmax : m.cq.hmax);
+    RetryPlan r;
+    retry_begin(r, s.c1psbits);
+    const bool subs0 = !r.work.empty();
+    if (subs0) KHIP_TRY(part_upload_plan(a, r.image));
+    std::vector<uint8_t> host_fail;
+    DevBuf dbgbuf;
+    if (probe) {
+      KHIP_TRY(dbgbuf.ensure(64));
+      KHIP_TRY_HIP(hipMemsetAsync(dbgbuf.p, 0, 64, a->stream));
+    }
+    PushInfo* pi = s.info();
+    const unsigned long long* c2 = pi->ctr;
+    int64_t added_total = 0;
+    C1Next next = C1_DONE;
+    for (int pass = 0;; pass++) {
+      unsigned long long* dbg = probe && pass == 0 ? dbgbuf.as<unsigned long long>() : nullptr;
+      if (pass > 0) KHIP_TRY_HIP(hipMemsetAsync(s.ctr.p, 0, CTR_PER_PASS * 8, a->stream));
+      const uint32_t* wk = (pass == 0 && !subs0) ? nullptr : s.work.as<uint32_t>();
+      const int64_t nwork = wk ? (int64_t)r.work.size() : g.P;
+      KHIP_TRY(c1_launch_merge(a, g, m, pass, wk, nwork, dbg));
+      const int nl = pass == 0 ? g.P : (int)r.plist.size();
+      hipLaunchKernelGGL(k_part_commit, dim3(ceil_div(std::max(nl, 1), 256)), dim3(256), 0, a->stream,
+                         pass == 0 ? (const int64_t*)g.ci : (const int64_t*)nullptr, g.P, s.pbase.as<int64_t>(),
+                         s.prn.as<uint32_t>(), pass == 0 ? nullptr : s.work.as<uint32_t>() + r.work.size(), nl,
+                         s.sel.as<uint8_t>(), s.cnt.as<int64_t>(), s.newcnt.as<unsigned long long>(),
+                         s.fail.as<uint8_t>(), s.ctr.as<unsigned long long>(), s.hcnt.as<unsigned long long>(),
+                         s.hnew.as<unsigned long long>());
+      KHIP_TRY_HIP(hipGetLastError());
+      if (pass == 0) {
+        ev_record_part(a, 3);
+        hipLaunchKernelGGL(k_part_stats, dim3(1), dim3(256), 0, a->stream, s.tpart.as<int64_t>(), g.nT,
+                           s.closed_ctr.as<unsigned long long>(), a->stream_time.as<int64_t>(),
+                           s.ctr.as<unsigned long long>());
+        KHIP_TRY_HIP(hipMemcpyAsync(pi->c1info, g.ci, CI_N * 8, hipMemcpyDeviceToHost, a->stream));
+      }
+      KHIP_TRY_HIP(hipMemcpyAsync(pi->ctr, s.ctr.p, CTR_COPIED * 8, hipMemcpyDeviceToHost, a->stream));
+      // the closed store's rows after this pass (closed rows leave in the pass that writes their
+      // item): read with the counters, no second round trip
+      KHIP_TRY_HIP(hipMemcpyAsync(&pi->closed_n, s.closed_ctr.p, 8, hipMemcpyDeviceToHost, a->stream));
+      KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
+      if (pass == 0 && pi->c1info[CI_GATE] == 0) {  // declined: nothing was written
+        KHIP_TRY(c1_declined_next(a, in, g, kretried, &next));
+        break;
+      }
+      if (pass == 0 && g.wide && ++s.c1_wide_n % 64 == 0) s.c1_wide = false;  // now and then: compact records again?
+      if (pass == 0 && !g.wide) {  // the next push's key base: this one's minimum, less a margin for keys below it
+        const int64_t km = pi->c1info[CI_KMINC], slack = (int64_t)1 << (g.val ? 26 : 28);
+        s.c1_kbase = km >= INT64_MIN + slack ? km - slack : km;
+        s.c1_kb_valid = true;
+      }
+      if (dbg) {
+        unsigned long long ph[8] = {};
+        if (hipMemcpy(ph, dbgbuf.p, sizeof(ph), hipMemcpyDeviceToHost) == hipSuccess) {
+          const double us = (double)std::min<int64_t>(g.P, 2 * s.n_cu) * 100.0;  // 100 MHz ticks → us per workgroup
+          fprintf(stderr, "[%s merge probe] per workgroup (us): start+evict %.1f records %.1f fold %.1f "
+                  "mark+count+reserve %.1f write %.1f\n", g.val ? "c1v" : "c1", ph[0] / us, ph[1] / us, ph[2] / us,
+                  ph[3] / us, ph[4] / us);
+        }
+      }
+      if (c2[CTR_NEED] & C1_FATAL)  // (cannot happen: the store holds every live row)
+        return fail(KHIP_E_DEVICE, "the closed store's capacity would be exceeded by a merge's closed rows");
+      added_total += (int64_t)c2[CTR_ADDED];
+      host_fail.clear();
+      if (c2[CTR_FAILED] != 0) {
+        host_fail.resize(g.P);
+        KHIP_TRY_HIP(hipMemcpy(host_fail.data(), s.fail.p, g.P, hipMemcpyDeviceToHost));
+      }
+#ifdef KHIP_TUNING
+      if (knob("KHIP_C1_TRACE", 0) != 0) {  // one line per pass: the tests' witness that a push was retried
+        int64_t nsub, ft, fr;
+        part_retry_trace_counts(r, wk != nullptr, host_fail, &nsub, &ft, &fr);
+        fprintf(stderr,
+                "[c1 trace] val=%d P=%d cmax=%lld log2H=%d pass=%d items=%lld sub_items=%lld failed=%llu fail_table=%lld "
+                "fail_region=%lld closed_before=%lld closed_after=%llu\n",
+                g.val ? 1 : 0, g.P, (long long)s.cmax, g.val ? m.v_log2H : m.log2H, pass, (long long)nwork,
+                (long long)nsub, c2[CTR_FAILED], (long long)ft, (long long)fr, (long long)s.closed_n, pi->closed_n);
+      }
+#endif
+      if (c2[CTR_FAILED] == 0) break;
+      KHIP_TRY(part_plan_retry(a, r, pass, host_fail));
+    }
+    if (next == C1_AGAIN_KBASE) {
+      kretried = true;
+      continue;
+    }
+    if (next == C1_AGAIN_WIDE && !wide_tried) {  // the keys needed the wide records: this push again with them
+      wide_tried = true;
+      kretried = false;
+      continue;
+    }
+    if (next != C1_DONE) {
+      *declined = true;
+      return KHIP_OK;
+    }
+    retry_learn(s.c1psbits, r);
+    s.res_fresh = false;
+    s.last_c1 = true;
+    // the closed store's rows after every pass (read with the last pass's counters)
+    part_push_epilogue(a, (int64_t)pi->closed_n, added_total, tot);
+    return KHIP_OK;
+  }
 }
 
 }  // namespace khip

@@ -494,6 +494,22 @@ struct InitWords {
   int64_t w[32];
 };
 
+// The partitioned engine's pinned block (PartState::pinfo): what a push copies back from the device
+// and the words it stages for the device.  A staging word shares no storage with anything a
+// device-to-host copy writes.
+constexpr int PINFO_CTR_WORDS = 13, PINFO_CI_WORDS = 24;  // = CTR_COPIED, CI_N (khip_part.hpp asserts it)
+struct PushInfo {
+  // device to host
+  int64_t wr[6];                             // k_part_wrange's wr[0..6) (part_push, read after the pass-0 sync)
+  unsigned long long ctr[PINFO_CTR_WORDS];   // the counter block after a pass (CTR_*)
+  int64_t c1info[PINFO_CI_WORDS];            // c1_push: the pipeline's c1info after pass 0 (CI_*)
+  unsigned long long closed_n;               // c1_push: the closed store's rows after a pass
+  // host to device
+  int64_t seed_st;                           // khip_agg.hip: the stream time before the batch
+  int64_t sup_after;                         // khip_agg.hip: the supplied stream time after it
+  unsigned long long having_closed;          // part_purge_closed: the kept closed rows passing HAVING
+};
+
 // Partitioned engine state (khip_agg_part.hip).
 struct PartState {
   int64_t P = 0;          // partitions (power of two), partition = top bits of mix64(key)
@@ -537,13 +553,14 @@ struct PartState {
   int8_t plane_w64[MAX_OPS] = {};
   int8_t word_op[32] = {};
   // the query's HAVING maintained on the device: rows passing it per partition (hcnt; hnew =
-  // being written this push), their sum (ctr[11]) and the closed store's (ctr[12]); having_total
+  // being written this push), their sum (CTR_HAVING_LIVE) and the closed store's (CTR_HAVING_CLOSED); having_total
   // = both, as of the last push.  hvalid = false once a push took a path that does not maintain
   // them (fallback kernel, split) until the next reset.
   DevBuf hcnt, hnew;
   int64_t having_total = 0;
   bool hvalid = true;
   HostBuf pinfo;  // pinned: push info (window range, event-time span) and end-of-push stats
+  PushInfo* info() const { return pinfo.as<PushInfo>(); }
   // COUNT(*) pipeline (khip_agg_c1.hip): bucket bases, the
   // refine's per-chunk partition offsets, records of each partition in the last push (prn), and
   // whether the last push took that pipeline (k_part_chg then reads prn instead of pbase)
@@ -551,7 +568,7 @@ struct PartState {
   DevBuf c1rc, c1rp, c1ro, c1scan, c1ci;  // step-run layout: [bucket][step] counts, their scan, step
                                           // offsets; per refine chunk its first step and run count
   int64_t c1_kbase = 0;             // key base for the next push's records (valid when c1_kb_valid)
-  bool c1_kb_valid = false, c1_kretry = false;
+  bool c1_kb_valid = false;
   int64_t c1_wide_n = 0;            // pushes with wide records (compact ones are tried every 64th)
   std::vector<uint8_t> c1psbits;    // the pipelines' sub-pass bits per partition (their own LDS tables)
   int64_t c1ps_hmax = 0, hint_groups = 1024;

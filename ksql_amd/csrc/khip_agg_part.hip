@@ -3214,7 +3214,7 @@ __global__ __launch_bounds__(1024) void k_part_wrange(const int64_t* __restrict_
       wr[7] = tb;
     }
   }
-  ctr[0] = ctr[1] = ctr[2] = 0ULL;
+  ctr[CTR_ADDED] = ctr[CTR_FAILED] = ctr[CTR_NEED] = 0ULL;
   if (closed_ctr) *closed_ctr = closed_n;
   int64_t lo = INT64_MAX, hi = INT64_MIN;
   if (mx >= 0) {  // some accepted record
@@ -3258,7 +3258,7 @@ __global__ __launch_bounds__(1024) void k_part_wrange(const int64_t* __restrict_
 
 // Publish the partitions processed in this pass (all touched ones, or the retry list).
 // gate (k_part_merge's pass 0): nothing to publish when k_part_wrange declined the merge.
-// out[11] = rows passing the query's HAVING over all live partitions (maintained: += new - old).
+// out[CTR_HAVING_LIVE] = rows passing the query's HAVING over all live partitions (maintained: += new - old).
 __global__ __launch_bounds__(256) void k_part_commit(const int64_t* __restrict__ gate, int P,
                                                      const int64_t* __restrict__ pbase,
                                                      const uint32_t* __restrict__ prn,
@@ -3294,14 +3294,14 @@ __global__ __launch_bounds__(256) void k_part_commit(const int64_t* __restrict__
   failed = wave_sum(failed);
   hdelta = wave_sum(hdelta);
   if ((threadIdx.x & 63) == 0) {
-    if (added) atomicAdd(&out[0], (unsigned long long)added);
-    if (failed) atomicAdd(&out[1], (unsigned long long)failed);
-    if (hdelta) atomicAdd(&out[11], (unsigned long long)hdelta);
+    if (added) atomicAdd(&out[CTR_ADDED], (unsigned long long)added);
+    if (failed) atomicAdd(&out[CTR_FAILED], (unsigned long long)failed);
+    if (hdelta) atomicAdd(&out[CTR_HAVING_LIVE], (unsigned long long)hdelta);
   }
 }
 
-// End-of-push counters in one place (one device-to-host copy per push): out[3 + k] = sum over
-// tiles of the per-tile counters k, out[3 + T_NPART] = closed rows, out[4 + T_NPART] = stream time.
+// End-of-push counters in one place (one device-to-host copy per push): out[CTR_TILE + k] = sum over
+// tiles of the per-tile counters k, out[CTR_CLOSED] = closed rows, out[CTR_STREAM_TIME] = stream time.
 __global__ __launch_bounds__(256) void k_part_stats(const int64_t* __restrict__ tpart, int64_t nT,
                                                     const unsigned long long* __restrict__ closed_n,
                                                     const int64_t* __restrict__ stream_time,
@@ -3316,10 +3316,10 @@ __global__ __launch_bounds__(256) void k_part_stats(const int64_t* __restrict__ 
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(&acc[k], (unsigned long long)v);
   }
   __syncthreads();
-  if (threadIdx.x < T_NPART) out[3 + threadIdx.x] = acc[threadIdx.x];
+  if (threadIdx.x < T_NPART) out[CTR_TILE + threadIdx.x] = acc[threadIdx.x];
   if (threadIdx.x == 0) {
-    out[3 + T_NPART] = closed_n ? *closed_n : 0ULL;
-    out[4 + T_NPART] = (unsigned long long)*stream_time;
+    out[CTR_CLOSED] = closed_n ? *closed_n : 0ULL;
+    out[CTR_STREAM_TIME] = (unsigned long long)*stream_time;
   }
 }
 
@@ -3568,13 +3568,13 @@ khip_status part_init(khip_agg* a, int64_t hint) {
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, a->device) == hipSuccess && ncu > 0)
       s.n_cu = ncu;
   }
-  KHIP_TRY(s.ctr.ensure(128));
+  KHIP_TRY(s.ctr.ensure(CTR_ALLOC * 8));
   KHIP_TRY(s.hcnt.ensure(s.P * 8));
   KHIP_TRY(s.hnew.ensure(s.P * 8));
-  KHIP_TRY(s.pinfo.ensure(512));
+  KHIP_TRY(s.pinfo.ensure(sizeof(PushInfo)));
   KHIP_TRY_HIP(hipMemsetAsync(s.hcnt.p, 0, s.P * 8, a->stream));
   KHIP_TRY_HIP(hipMemsetAsync(s.hnew.p, 0, s.P * 8, a->stream));
-  KHIP_TRY_HIP(hipMemsetAsync(s.ctr.p, 0, 128, a->stream));
+  KHIP_TRY_HIP(hipMemsetAsync(s.ctr.p, 0, CTR_ALLOC * 8, a->stream));
   s.having_total = 0;
   s.hvalid = true;
   for (int b = 0; b < 2; b++) KHIP_TRY(s.buf[b].ensure((size_t)s.P * s.cmax * a->sw * 8));
@@ -3612,7 +3612,7 @@ __global__ __launch_bounds__(256) void k_part_reset(int64_t P, unsigned long lon
     newcnt[p] = 0;
     fail[p] = 0;
   }
-  if (p < 16) ctr[p] = 0;
+  if (p < CTR_ALLOC) ctr[p] = 0;
   if (p == 0) *stream_time = -1;
 }
 
@@ -3625,7 +3625,7 @@ khip_status part_reset(khip_agg* a) {
   s.having_total = 0;
   s.last_c1 = false;
   s.c1_skip = 0;  // (c1_wide, a prediction about the keys, stays)
-  hipLaunchKernelGGL(k_part_reset, dim3(ceil_div(std::max<int64_t>(s.P, 16), 256)), dim3(256), 0, a->stream, s.P,
+  hipLaunchKernelGGL(k_part_reset, dim3(ceil_div(std::max<int64_t>(s.P, CTR_ALLOC), 256)), dim3(256), 0, a->stream, s.P,
                      s.hcnt.as<unsigned long long>(), s.hnew.as<unsigned long long>(), s.cnt.as<int64_t>(),
                      s.newcnt.as<unsigned long long>(), s.fail.as<uint8_t>(), s.ctr.as<unsigned long long>(),
                      a->stream_time.as<int64_t>());
@@ -3677,16 +3677,8 @@ khip_status part_regrow(khip_agg* a, int64_t ncmax) {
   }
   KHIP_TRY_HIP(hipMemsetAsync(s.sel.p, 0, s.P, a->stream));
   KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
-  for (int b = 0; b < 2; b++) {
-    s.buf[b].release();
-    s.buf[b] = std::move(nb[b]);
-    nb[b].p = nullptr;
-  }
-  if (a->changelog) {
-    a->chg.release();
-    a->chg = std::move(nchg);
-    nchg.p = nullptr;
-  }
+  for (int b = 0; b < 2; b++) s.buf[b] = std::move(nb[b]);
+  if (a->changelog) a->chg = std::move(nchg);
   s.cmax = ncmax;
   return KHIP_OK;
 }
@@ -3720,11 +3712,7 @@ static khip_status part_split(khip_agg* a) {
   KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
   DevBuf* olds[] = {&s.buf[0], &s.buf[1], &s.cnt, &s.sel, &s.newcnt, &s.fail};
   DevBuf* news[] = {&nb[0], &nb[1], &ncnt, &nsel, &nnew, &nfail};
-  for (int k = 0; k < 6; k++) {
-    olds[k]->release();
-    *olds[k] = std::move(*news[k]);
-    news[k]->p = nullptr;
-  }
+  for (int k = 0; k < 6; k++) *olds[k] = std::move(*news[k]);
   // a child holds about half of its parent's groups: one sub-pass bit fewer
   std::vector<uint8_t> nps(P2);
   for (int64_t c = 0; c < P2; c++) nps[c] = s.psbits[c >> 1] ? (uint8_t)(s.psbits[c >> 1] - 1) : 0;
@@ -3767,6 +3755,74 @@ static void agg_probe_report(DevBuf& b, int nb) {
           m, nb, (hi - lo) / 100.0, ph[0] / m / 100, ph[1] / m / 100, ph[2] / m / 100, ph[3] / m / 100, ph[4] / m / 100);
 }
 
+// ---- the steps part_push and c1_push share (the retry protocol: DESIGN.md (d))
+
+// The closed store holds closed_n + live rows: worst case every live row closes in this push.
+khip_status part_grow_closed(khip_agg* a) {
+  PartState& s = a->part;
+  const int64_t live = a->occ - s.closed_n;
+  if (s.closed_cap >= s.closed_n + live) return KHIP_OK;
+  const int64_t ncap = next_pow2(std::max<int64_t>(1024, s.closed_n + live));
+  DevBuf nc;
+  KHIP_TRY(nc.ensure((size_t)ncap * a->sw * 8));
+  if (s.closed_n)
+    KHIP_TRY_HIP(hipMemcpyAsync(nc.p, s.closed.p, (size_t)s.closed_n * a->sw * 8, hipMemcpyDeviceToDevice, a->stream));
+  KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
+  s.closed = std::move(nc);
+  s.closed_cap = ncap;
+  return KHIP_OK;
+}
+
+// A pass's work items (followed by its partition list) → the device's work buffer.
+khip_status part_upload_plan(khip_agg* a, const std::vector<uint32_t>& image) {
+  PartState& s = a->part;
+  KHIP_TRY(s.work.ensure(image.size() * 4));
+  KHIP_TRY_HIP(hipMemcpyAsync(s.work.p, image.data(), image.size() * 4, hipMemcpyHostToDevice, a->stream));
+  return KHIP_OK;
+}
+
+// After a pass with failed partitions (host_fail = its fail[]): plan the next one, grow the regions
+// when one overflowed, upload the plan.
+khip_status part_plan_retry(khip_agg* a, RetryPlan& r, int pass, const std::vector<uint8_t>& host_fail) {
+  PartState& s = a->part;
+  if (pass > 24) return fail(KHIP_E_DEVICE, "partitioned aggregation could not place the batch");
+  KHIP_TRY_HIP(hipMemsetAsync(s.fail.p, 0, s.P, a->stream));
+  if (!retry_next(r, host_fail.data(), (int)s.P))
+    return fail(KHIP_E_DEVICE, "partition needs more than 4096 sub-passes (extreme key skew)");
+  // grow straight to what the largest overflowing partition needed (sub-passes of one
+  // partition append to the same region, so its full row count is at least `need`)
+  if (r.grow) {
+    const int64_t need = (int64_t)s.info()->ctr[CTR_NEED];
+    KHIP_TRY(part_regrow(a, next_pow2(std::max<int64_t>(s.cmax * 2, need * 5 / 4 + 64))));
+  }
+  return part_upload_plan(a, r.image);
+}
+
+// A trace line's counts: the pass's items with sub-passes (listed: it ran r.work) and the
+// partitions it failed by cause.
+void part_retry_trace_counts(const RetryPlan& r, bool listed, const std::vector<uint8_t>& host_fail, int64_t* nsub,
+                             int64_t* fail_table, int64_t* fail_region) {
+  *nsub = *fail_table = *fail_region = 0;
+  if (listed)
+    for (const uint32_t x : r.work) *nsub += work_sbits(x) != 0;
+  for (const uint8_t f : host_fail) *fail_table += (f & FAIL_TABLE) != 0, *fail_region += (f & FAIL_REGION) != 0;
+}
+
+// End of a push: the last pass's counter copy → tot[], the HAVING total, the closed store's row
+// count (closed_now: each driver's own word) and the stream time.
+void part_push_epilogue(khip_agg* a, int64_t closed_now, int64_t added, int64_t* tot) {
+  PartState& s = a->part;
+  const unsigned long long* c = s.info()->ctr;
+  s.having_total = (int64_t)(c[CTR_HAVING_LIVE] + c[CTR_HAVING_CLOSED]);
+  added += closed_now - s.closed_n;  // evicted rows left the live regions but are still groups
+  s.closed_n = closed_now;
+  a->host_stream_time = (int64_t)c[CTR_STREAM_TIME];
+  static_assert(P_ACCEPTED == T_ACCEPTED && P_NULL_KEY == T_NULL_KEY && P_NULL_ROW == T_NULL_ROW &&
+                P_BAD_TS == T_BAD_TS && P_APPLIED == T_APPLIED && P_LATE == T_LATE, "tile counter k is tot[k]");
+  for (int k = 0; k < T_NPART; k++) tot[k] += (int64_t)c[CTR_TILE + k];
+  tot[P_NEW] += added;
+}
+
 // One push slice (n < 2^31).  tot[] receives the P_* counters.
 // Shuffled rows (khip_agg_push_shuffled) through the value pipeline, read where they lie; *done =
 // false when the pipeline does not apply or declined the push (the caller unpacks the rows and
@@ -3783,10 +3839,10 @@ khip_status part_push_rows(khip_agg* a, int64_t n, const RowsIn& ri, int key_col
   RowsIn r = ri;
   r.vword = vcol == key_col ? 0 : 2 + vcol - (vcol > key_col ? 1 : 0);
   r.vbit = vcol;
-  bool declined = false, retry_wide = false;
+  bool declined = false;
   // st_at only selects the stream-time scatter here (never read as a column: ROWS reads the word)
   const int64_t* st_flag = supplied ? (const int64_t*)ri.rows : nullptr;
-  KHIP_TRY(c1_push(a, n, nullptr, nullptr, nullptr, nullptr, tot, &declined, st_flag, &retry_wide, nullptr, vcol, &r));
+  KHIP_TRY(c1_push(a, n, C1In{nullptr, nullptr, nullptr, nullptr, st_flag, nullptr, vcol, &r}, tot, &declined));
   if (a->profile) (declined ? a->times.c1_declined : a->times.c1_pushes)++;
   if (declined) s.c1_skip = 8;
   *done = !declined;
@@ -3809,10 +3865,8 @@ khip_status part_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t
   } else if (c1_eligible(a, n) || c1v_eligible(a, n, &vcol)) {
     // COUNT(*) alone: 8-byte records; one argument column: 16-byte value records
     const ColPtrs* vc = vcol >= 0 ? &cols : nullptr;
-    bool declined = false, retry_wide = false;
-    KHIP_TRY(c1_push(a, n, keys, ts, kv, rv, tot, &declined, st_at, &retry_wide, vc, vcol));
-    if (declined && retry_wide)  // the keys needed the wide records: this push again with them
-      KHIP_TRY(c1_push(a, n, keys, ts, kv, rv, tot, &declined, st_at, &retry_wide, vc, vcol));
+    bool declined = false;
+    KHIP_TRY(c1_push(a, n, C1In{keys, ts, kv, rv, st_at, vc, vcol, nullptr}, tot, &declined));
     if (a->profile) (declined ? a->times.c1_declined : a->times.c1_pushes)++;
     if (!declined) return KHIP_OK;
     s.c1_skip = 8;
@@ -3904,8 +3958,8 @@ khip_status part_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t
                      a->windowed ? s.closed_ctr.as<unsigned long long>() : (unsigned long long*)nullptr,
                      (unsigned long long)s.closed_n, s.tilekr.as<int64_t>(), r8_allow ? 1 : 0);
   s.res_fresh = false;
-  int64_t* pin = s.pinfo.as<int64_t>();  // wr[0..6), read after the pass-0 sync
-  KHIP_TRY_HIP(hipMemcpyAsync(pin, s.wr.p, 48, hipMemcpyDeviceToHost, a->stream));
+  int64_t* pin = s.info()->wr;  // wr[0..6), read after the pass-0 sync
+  KHIP_TRY_HIP(hipMemcpyAsync(pin, s.wr.p, sizeof(s.info()->wr), hipMemcpyDeviceToHost, a->stream));
   // 2. offsets
   hipLaunchKernelGGL(k_part_colsum, dim3(ceil_div(P, 256), TC), dim3(256), 0, a->stream, s.hist.as<uint32_t>(), nT, P,
                      TC, s.scan_tmp.as<int64_t>());
@@ -4056,39 +4110,21 @@ khip_status part_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t
     mq.r12 = r12_merge ? 1 : 0;
     mq.chg = a->changelog ? a->chg.as<uint8_t>() : nullptr;
   }
-  if (a->windowed) {  // worst case every live row closes in this push
-    const int64_t live = a->occ - s.closed_n;
-    if (s.closed_cap < s.closed_n + live) {
-      const int64_t ncap = next_pow2(std::max<int64_t>(1024, s.closed_n + live));
-      DevBuf nc;
-      KHIP_TRY(nc.ensure((size_t)ncap * a->sw * 8));
-      if (s.closed_n)
-        KHIP_TRY_HIP(hipMemcpyAsync(nc.p, s.closed.p, (size_t)s.closed_n * a->sw * 8, hipMemcpyDeviceToDevice, a->stream));
-      KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
-      s.closed.release();
-      s.closed = std::move(nc);
-      nc.p = nullptr;
-      s.closed_cap = ncap;
-    }
-  }
+  if (a->windowed) KHIP_TRY(part_grow_closed(a));
   int64_t added_total = 0;
   std::vector<uint8_t> host_fail;
-  std::vector<int> sbits(s.psbits.begin(), s.psbits.end());
-  std::vector<uint32_t> plist, work;
   // pass 0: one work item per partition, or its learned 2^sbits sub-passes
-  bool subs0 = false;
-  for (int p = 0; p < P && !subs0; p++) subs0 = sbits[p] > 0;
-  if (subs0) {
-    for (int p = 0; p < P; p++)
-      for (int k = 0; k < (1 << sbits[p]); k++) work.push_back((uint32_t)p | ((uint32_t)sbits[p] << 16) | ((uint32_t)k << 20));
-    KHIP_TRY(s.work.ensure(work.size() * 4));
-    KHIP_TRY_HIP(hipMemcpyAsync(s.work.p, work.data(), work.size() * 4, hipMemcpyHostToDevice, a->stream));
-  }
+  RetryPlan r;
+  retry_begin(r, s.psbits);
+  const std::vector<uint32_t>& work = r.work;
+  const bool subs0 = !work.empty();
+  if (subs0) KHIP_TRY(part_upload_plan(a, r.image));
   // KHIP_AGG_PROBE=1: per-workgroup phase timestamps of pass 0 (wall clock, 100 MHz) → stderr
   const bool probe = knob("KHIP_AGG_PROBE", 0) != 0;
   DevBuf dbgbuf;
   unsigned long long* dbg = nullptr;
   bool c1_ran = false;
+  const int c1h = (int)knob("KHIP_C1_LOG2H", 12);  // the lean COUNT(*) merge's table
   for (int pass = 0;; pass++) {
     PartAggParams q = q0;
     dbg = nullptr;
@@ -4100,11 +4136,10 @@ khip_status part_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t
     q.cmax = s.cmax;
     mq.cmax = s.cmax;
     q.chg = mq.chg = a->changelog ? a->chg.as<uint8_t>() : nullptr;  // a retry's regrow moves them
-    if (pass > 0) KHIP_TRY_HIP(hipMemsetAsync(s.ctr.p, 0, 24, a->stream));  // pass 0: k_part_wrange
+    if (pass > 0) KHIP_TRY_HIP(hipMemsetAsync(s.ctr.p, 0, CTR_PER_PASS * 8, a->stream));  // pass 0: k_part_wrange
     const uint32_t* wk = (pass == 0 && !subs0) ? nullptr : s.work.as<uint32_t>();
     const int64_t nwork = (pass == 0 && !subs0) ? P : (int64_t)work.size();
     if (merge) {
-      const int c1h = (int)knob("KHIP_C1_LOG2H", 12);
       c1_ran = c1_plan;
       if (c1_ran) {  // the lean COUNT(*) merge
         const int au = (int)knob("KHIP_C1_AU", 6);
@@ -4131,9 +4166,9 @@ khip_status part_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t
         hipLaunchKernelGGL(mk, dim3(grid), dim3(512), lds, a->stream, cq, wk, nwork, s.pbase.as<int64_t>(),
                            s.srec.as<uint64_t>(), pass == 0 ? 1 : 0, s.buf[0].as<uint64_t>(), s.buf[1].as<uint64_t>(),
                            s.sel.as<uint8_t>(), s.cnt.as<int64_t>(), s.newcnt.as<unsigned long long>(),
-                           s.fail.as<uint8_t>(), s.ctr.as<unsigned long long>() + 2, close0, s.closed.as<uint64_t>(),
+                           s.fail.as<uint8_t>(), s.ctr.as<unsigned long long>() + CTR_NEED, close0, s.closed.as<uint64_t>(),
                            s.closed_ctr.as<unsigned long long>(), s.wr.as<int64_t>(),
-                           s.hnew.as<unsigned long long>(), s.ctr.as<unsigned long long>() + 12, dbg);
+                           s.hnew.as<unsigned long long>(), s.ctr.as<unsigned long long>() + CTR_HAVING_CLOSED, dbg);
         }
       } else {
       auto mk = mq.r12 ? (mt >= 512 ? (cnt1 ? k_part_merge<true, 512, true> : k_part_merge<false, 512, true>)
@@ -4145,9 +4180,9 @@ khip_status part_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t
       hipLaunchKernelGGL(mk, dim3(grid), dim3(mt >= 512 ? 512 : 256), s.m_lds, a->stream, mq, wk, nwork, s.pbase.as<int64_t>(),
                          s.srec.as<uint64_t>(), pass == 0 ? 1 : 0, s.buf[0].as<uint64_t>(), s.buf[1].as<uint64_t>(),
                          s.sel.as<uint8_t>(), s.cnt.as<int64_t>(), s.newcnt.as<unsigned long long>(),
-                         s.fail.as<uint8_t>(), s.ctr.as<unsigned long long>() + 2, close0, s.closed.as<uint64_t>(),
+                         s.fail.as<uint8_t>(), s.ctr.as<unsigned long long>() + CTR_NEED, close0, s.closed.as<uint64_t>(),
                          s.closed_ctr.as<unsigned long long>(), s.wr.as<int64_t>(),
-                         s.hnew.as<unsigned long long>(), s.ctr.as<unsigned long long>() + 12, dbg);
+                         s.hnew.as<unsigned long long>(), s.ctr.as<unsigned long long>() + CTR_HAVING_CLOSED, dbg);
       }
     } else {
       hipFuncSetAttribute((const void*)k_part_agg, hipFuncAttributeMaxDynamicSharedMemorySize, s.lds_bytes);
@@ -4155,10 +4190,10 @@ khip_status part_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t
                          s.pbase.as<int64_t>(), s.srec.as<uint64_t>(), pass == 0 ? 1 : 0, s.buf[0].as<uint64_t>(),
                          s.buf[1].as<uint64_t>(), s.sel.as<uint8_t>(), s.cnt.as<int64_t>(),
                          s.newcnt.as<unsigned long long>(), s.fail.as<uint8_t>(),
-                         s.ctr.as<unsigned long long>() + 2, close0, s.closed.as<uint64_t>(),
+                         s.ctr.as<unsigned long long>() + CTR_NEED, close0, s.closed.as<uint64_t>(),
                          s.closed_ctr.as<unsigned long long>(), s.wr.as<int64_t>(), dbg);
     }
-    const int nl = pass == 0 ? P : (int)plist.size();
+    const int nl = pass == 0 ? P : (int)r.plist.size();
     hipLaunchKernelGGL(k_part_commit, dim3(ceil_div(std::max(nl, 1), 256)), dim3(256), 0, a->stream,
                        (merge && pass == 0) ? s.wr.as<int64_t>() : (const int64_t*)nullptr, P,
                        s.pbase.as<int64_t>(), (const uint32_t*)nullptr,
@@ -4173,8 +4208,8 @@ khip_status part_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t
                          a->windowed ? s.closed_ctr.as<unsigned long long>() : (unsigned long long*)nullptr,
                          a->stream_time.as<int64_t>(), s.ctr.as<unsigned long long>());
     }
-    unsigned long long* c2 = s.pinfo.as<unsigned long long>() + 8;
-    KHIP_TRY_HIP(hipMemcpyAsync(c2, s.ctr.p, 13 * 8, hipMemcpyDeviceToHost, a->stream));
+    const unsigned long long* c2 = s.info()->ctr;
+    KHIP_TRY_HIP(hipMemcpyAsync(s.info()->ctr, s.ctr.p, CTR_COPIED * 8, hipMemcpyDeviceToHost, a->stream));
     KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
     if (pass == 0 && merge && pin[4] == 0) {  // declined on the device: nothing was written
       merge = false;
@@ -4182,7 +4217,7 @@ khip_status part_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t
       pass = -1;
       continue;
     }
-    added_total += (int64_t)c2[0];
+    added_total += (int64_t)c2[CTR_ADDED];
     if (dbg && merge) {  // k_part_merge: per-phase time summed over its persistent workgroups
       unsigned long long ph[8] = {};
       if (hipMemcpy(ph, dbgbuf.p, sizeof(ph), hipMemcpyDeviceToHost) == hipSuccess) {
@@ -4197,54 +4232,31 @@ khip_status part_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t
     } else if (dbg) {
       agg_probe_report(dbgbuf, (int)((pass == 0 && !subs0) ? P : (int64_t)work.size()));
     }
-    if (c2[1] == 0) break;
-    if (pass > 24) return fail(KHIP_E_DEVICE, "partitioned aggregation could not place the batch");
-    // retry the failed partitions: LDS overflow → twice the sub-passes; region overflow → grow
-    host_fail.resize(P);
-    KHIP_TRY_HIP(hipMemcpy(host_fail.data(), s.fail.p, P, hipMemcpyDeviceToHost));
-    KHIP_TRY_HIP(hipMemsetAsync(s.fail.p, 0, P, a->stream));
-    bool grow = false;
-    plist.clear();
-    work.clear();
-    for (int p = 0; p < P; p++) {
-      if (!host_fail[p]) continue;
-      if (host_fail[p] & 1) sbits[p] = sbits[p] + 1;
-      if (host_fail[p] & 2) grow = true;
-      plist.push_back((uint32_t)p);
-      if (sbits[p] > 12) return fail(KHIP_E_DEVICE, "partition needs more than 4096 sub-passes (extreme key skew)");
-      for (int k = 0; k < (1 << sbits[p]); k++) work.push_back((uint32_t)p | ((uint32_t)sbits[p] << 16) | ((uint32_t)k << 20));
+    host_fail.clear();
+    if (c2[CTR_FAILED] != 0) {
+      host_fail.resize(P);
+      KHIP_TRY_HIP(hipMemcpy(host_fail.data(), s.fail.p, P, hipMemcpyDeviceToHost));
     }
-    // grow straight to what the largest overflowing partition needed (sub-passes of one
-    // partition append to the same region, so its full row count is at least `need`)
-    if (grow) KHIP_TRY(part_regrow(a, next_pow2(std::max<int64_t>(s.cmax * 2, (int64_t)c2[2] * 5 / 4 + 64))));
-    std::vector<uint32_t> both(work);
-    both.insert(both.end(), plist.begin(), plist.end());
-    KHIP_TRY(s.work.ensure(both.size() * 4));
-    KHIP_TRY_HIP(hipMemcpyAsync(s.work.p, both.data(), both.size() * 4, hipMemcpyHostToDevice, a->stream));
+#ifdef KHIP_TUNING
+    if (knob("KHIP_PART_TRACE", 0) != 0) {  // one line per pass, as c1_push's [c1 trace]
+      int64_t nsub, ft, fr;
+      part_retry_trace_counts(r, wk != nullptr, host_fail, &nsub, &ft, &fr);
+      const int H = !merge ? s.H : (c1_ran ? 1 << c1h : s.mH);  // the kernel's LDS table (entries)
+      fprintf(stderr,
+              "[part trace] kernel=%s P=%d cmax=%lld H=%d pass=%d items=%lld sub_items=%lld failed=%llu "
+              "fail_table=%lld fail_region=%lld closed_before=%lld closed_after=%llu\n",
+              !merge ? "agg" : (c1_ran ? "merge_c1" : "merge"), P, (long long)s.cmax, H, pass, (long long)nwork, (long long)nsub, c2[CTR_FAILED], (long long)ft, (long long)fr,
+              (long long)s.closed_n, a->windowed ? c2[CTR_CLOSED] : 0ULL);
+    }
+#endif
+    if (c2[CTR_FAILED] == 0) break;
+    // retry the failed partitions: LDS overflow → twice the sub-passes; region overflow → grow
+    KHIP_TRY(part_plan_retry(a, r, pass, host_fail));
   }
-  for (int p = 0; p < P; p++) s.psbits[p] = (uint8_t)std::max<int>(s.psbits[p], sbits[p]);
+  retry_learn(s.psbits, r);
   if (!merge) s.hvalid = false;
-  {
-    const unsigned long long* hc = s.pinfo.as<unsigned long long>() + 8;
-    s.having_total = (int64_t)(hc[11] + hc[12]);  // live rows + closed rows passing HAVING
-  }
   // 5. counters (k_part_stats after pass 0: evictions only happen there)
-  const unsigned long long* st = s.pinfo.as<unsigned long long>() + 8;
-  if (a->windowed) {
-    const int64_t cn = (int64_t)st[3 + T_NPART];
-    added_total += cn - s.closed_n;  // evicted rows left the live regions but are still groups
-    s.closed_n = cn;
-  }
-  a->host_stream_time = (int64_t)st[4 + T_NPART];
-  int64_t c[T_NPART];
-  for (int k = 0; k < T_NPART; k++) c[k] = (int64_t)st[3 + k];
-  tot[P_ACCEPTED] += c[T_ACCEPTED];
-  tot[P_NULL_KEY] += c[T_NULL_KEY];
-  tot[P_NULL_ROW] += c[T_NULL_ROW];
-  tot[P_BAD_TS] += c[T_BAD_TS];
-  tot[P_APPLIED] += c[T_APPLIED];
-  tot[P_LATE] += c[T_LATE];
-  tot[P_NEW] += added_total;
+  part_push_epilogue(a, a->windowed ? (int64_t)s.info()->ctr[CTR_CLOSED] : s.closed_n, added_total, tot);
   return KHIP_OK;
 }
 
@@ -4369,7 +4381,7 @@ khip_status part_changes(khip_agg* a, std::vector<uint64_t>* rows, std::vector<u
 }
 
 // Retention: drop the closed store's rows that expired from the window store (vis: h.vis_from),
-// keeping the maintained HAVING count of the closed rows (ctr[12]) and the group count in step.
+// keeping the maintained HAVING count of the closed rows (CTR_HAVING_CLOSED) and the group count in step.
 khip_status part_purge_closed(khip_agg* a, const HavingDev& vis) {
   PartState& s = a->part;
   if (s.closed_n == 0 || vis.vis_from <= s.purged_to) return KHIP_OK;
@@ -4399,11 +4411,12 @@ khip_status part_purge_closed(khip_agg* a, const HavingDev& vis) {
   s.purged_to = vis.vis_from;
   const int64_t keep = kc[0];
   if (keep == s.closed_n) return KHIP_OK;  // nothing expired: the store stays (its copy is unused)
-  if (vh.active) {  // ctr[12]: closed rows passing HAVING
-    unsigned long long* hc = s.pinfo.as<unsigned long long>() + 40;
+  if (vh.active) {
+    unsigned long long* hc = &s.info()->having_closed;
     *hc = (unsigned long long)kc[1];
-    KHIP_TRY_HIP(hipMemcpyAsync(s.ctr.as<unsigned long long>() + 12, hc, 8, hipMemcpyHostToDevice, a->stream));
-    s.having_total += kc[1] - (int64_t)s.pinfo.as<unsigned long long>()[8 + 12];
+    KHIP_TRY_HIP(hipMemcpyAsync(s.ctr.as<unsigned long long>() + CTR_HAVING_CLOSED, hc, 8, hipMemcpyHostToDevice,
+                                a->stream));
+    s.having_total += kc[1] - (int64_t)s.info()->ctr[CTR_HAVING_CLOSED];
     KHIP_TRY_HIP(hipStreamSynchronize(a->stream));  // (hc is pinned host memory the next push reuses)
   }
   std::swap(s.closed, s.closed2);

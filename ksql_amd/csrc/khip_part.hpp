@@ -3,10 +3,57 @@
 #pragma once
 
 #include "khip_agg_internal.hpp"
+#include "khip_retry.hpp"
 
 namespace khip {
 
 enum { T_ACCEPTED, T_NULL_KEY, T_NULL_ROW, T_BAD_TS, T_APPLIED, T_LATE, T_NPART };
+
+// The device counter block (PartState::ctr, u64 words), copied to PushInfo::ctr after every pass.
+enum {
+  CTR_ADDED = 0,                   // groups added by the pass (k_part_commit)
+  CTR_FAILED = 1,                  // partitions that failed the pass (k_part_commit)
+  CTR_NEED = 2,                    // region rows the largest overflowing partition needed (| C1_FATAL)
+  CTR_TILE = 3,                    // [T_NPART] the tiles' counters, summed (k_part_stats)
+  CTR_PER_PASS = CTR_TILE,         // the words before are cleared for every pass
+  CTR_CLOSED = CTR_TILE + T_NPART,  // closed rows (k_part_stats)
+  CTR_STREAM_TIME,                 // stream time after the push (k_part_stats)
+  CTR_HAVING_LIVE,                 // live rows passing the query's HAVING (maintained: += new - old)
+  CTR_HAVING_CLOSED,               // closed rows passing it
+  CTR_COPIED,                      // words the host reads back
+  CTR_ALLOC = 16                   // words allocated (and zeroed by a reset)
+};
+static_assert(CTR_HAVING_LIVE == 11 && CTR_HAVING_CLOSED == 12, "the counter block's layout");
+static_assert(CTR_COPIED == PINFO_CTR_WORDS && CTR_COPIED <= CTR_ALLOC, "the counter copy fits its buffers");
+// in the CTR_NEED word: a reservation past the closed store's capacity
+constexpr unsigned long long C1_FATAL = 1ULL << 63;
+
+// c1info (int64) slots of the COUNT(*) / value pipelines (khip_agg_c1.hip)
+enum {
+  CI_KMIN = 0,   // atomics (the scatters), reset by k_c1_check for the next push
+  CI_KMAX = 1,
+  CI_TFAIL = 2,  // some accepted ts - T0 outside int32 (k_c1_scatter)
+  CI_T0 = 3,     // time base (the scatters' block 0)
+  CI_GATE = 4,   // accepted (k_part_commit reads gate[4])
+  CI_WBASE = 5,  // smallest window index (records and live resident rows)
+  CI_WBITS = 6,
+  CI_ID32 = 7,   // identity mode: 1 = u32 (krel << wbits | wrel), 0 = u64 (krel << 32 | wrel)
+  CI_TMIN = 8,   // smallest accepted ts (row-time deltas are relative to it)
+  CI_TMAX = 9,
+  CI_KBITS = 10,
+  CI_NCHUNK = 11,  // refine work items
+  CI_KMINC = 12,   // kmin copied for the refine / merge
+  CI_WHI = 13,     // largest relative window index
+  CI_KRANGE = 14,
+  CI_WIDE = 15,    // records of this push: 1 = key hash + u32 ts words (the key range is too wide)
+  CI_REASON = 16,  // declined: 1 = the key range needs the wide records (the host retries with them)
+  CI_FITS = 17,    // the key range fits the compact records (a wide push tells the host)
+  CI_KBASE = 18,   // the key base of this push's records (the scatters)
+  CI_KSHIFT = 19,  // kmin - kbase: the refines rebase the records to the key minimum
+  CI_KFAIL = 20,   // some key fell outside the records' key field above kbase (the scatters)
+  CI_N = 24
+};
+static_assert(CI_N == PINFO_CI_WORDS, "PushInfo holds a c1info copy");
 
 // Key hash: its top log2P bits pick the partition; inside a partition the LDS slot and the
 // sub-pass of a (key, windowStart) group mix its low bits with ws (cheap 32-bit math).
@@ -173,13 +220,26 @@ __device__ __forceinline__ void stage_step_r8(const int64_t (&rec)[U], const uin
 __global__ void k_part_pscan(int64_t* __restrict__ v, int64_t n);
 __global__ void k_part_stats(const int64_t* __restrict__ tpart, int64_t nT, const unsigned long long* __restrict__ closed_n,
                              const int64_t* __restrict__ stream_time, unsigned long long* __restrict__ out);
-khip_status part_regrow(khip_agg* a, int64_t ncmax);
+// the steps of a push both drivers take (khip_agg_part.hip; the retry protocol: DESIGN.md (d))
+khip_status part_grow_closed(khip_agg* a);
+khip_status part_upload_plan(khip_agg* a, const std::vector<uint32_t>& image);
+khip_status part_plan_retry(khip_agg* a, RetryPlan& r, int pass, const std::vector<uint8_t>& host_fail);
+void part_retry_trace_counts(const RetryPlan& r, bool listed, const std::vector<uint8_t>& host_fail, int64_t* nsub,
+                             int64_t* fail_table, int64_t* fail_region);
+void part_push_epilogue(khip_agg* a, int64_t closed_now, int64_t added, int64_t* tot);
 // khip_agg_c1.hip: the windowed COUNT(*) pipeline (declined = the general path must run)
 bool c1_eligible(khip_agg* a, int64_t n);
 bool c1v_eligible(khip_agg* a, int64_t n, int* col);
-khip_status c1_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t* ts, const uint8_t* kv,
-                    const uint8_t* rv, int64_t* tot, bool* declined, const int64_t* st_at, bool* retry_wide,
-                    const ColPtrs* cols = nullptr, int vcol = -1, const RowsIn* rows = nullptr);
+// One push's input.  cols or rows set: the value pipeline over argument column vcol (c1v_eligible).
+struct C1In {
+  const int64_t *keys, *ts;
+  const uint8_t *kv, *rv;
+  const int64_t* st_at;
+  const ColPtrs* cols;
+  int vcol;
+  const RowsIn* rows;
+};
+khip_status c1_push(khip_agg* a, int64_t n, const C1In& in, int64_t* tot, bool* declined);
 __global__ void k_part_commit(const int64_t* __restrict__ gate, int P, const int64_t* __restrict__ pbase,
                               const uint32_t* __restrict__ prn, const uint32_t* __restrict__ plist, int nlist,
                               uint8_t* __restrict__ sel, int64_t* __restrict__ cnt,

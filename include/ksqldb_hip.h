@@ -48,7 +48,12 @@ typedef int32_t khip_status;
                                    windows, KHIP_FLAG_TABLE_SOURCE, a HAVING on the offset
                                    aggregate itself, more user + hidden sequence columns
                                    than 8, and khip_agg_push_shuffled on such a handle; the
-                                   N forms (arrays) are never routed here                   */
+                                   N forms (arrays) are never routed here.
+                                   TOPK / TOPKDISTINCT: the struct form topk(col, other...,
+                                   k), a STRING / DECIMAL / DATE / TIME / TIMESTAMP / BYTES
+                                   argument (never routed here), SESSION windows,
+                                   KHIP_FLAG_TABLE_SOURCE, a HAVING on the TOPK aggregate
+                                   itself, and a k whose slots exceed the 29 state words     */
 #define KHIP_E_BUFFER (-5)      /* caller-provided output buffer too small                  */
 #define KHIP_E_COMM (-6)        /* RCCL error                                                */
 #define KHIP_E_STATE (-7)       /* call not valid in the handle's current state             */
@@ -98,6 +103,23 @@ typedef int32_t khip_status;
 #define KHIP_AGG_EARLIEST_BY_OFFSET 7
 /* OR-ed into khip_agg_spec.kind of the two kinds above: ignoreNulls = false */
 #define KHIP_AGG_KEEP_NULLS 0x100
+/* TOPK(col, k) / TOPKDISTINCT(col, k), col INTEGER / BIGINT / DOUBLE, literal k >= 1 OR-ed into
+ * khip_agg_spec.kind with KHIP_AGG_K(k): function/udaf/topk/TopkKudaf.java:119-142 (aggregate),
+ * :145-184 (merge); function/udaf/topkdistinct/TopkDistinctKudaf.java:130-153, :156-182.  NULL
+ * arguments are skipped.  The result is an ARRAY of the argument's type (SqlArray.of(inputType),
+ * TopkKudaf.java:104-110): the group's k largest values in descending compareTo order, fewer while
+ * the group has seen fewer, [] (never SQL NULL) when every argument was NULL.  TOPK keeps
+ * duplicates (the multiset top k); TOPKDISTINCT keeps one copy per value, equality being equals():
+ * for DOUBLE every NaN is one value (returned as the canonical NaN, above +Infinity) and -0.0 is
+ * not 0.0.  How the array is laid out in a khip_snapshot: see khip_snapshot below.
+ * KHIP_E_INVALID: k < 1, KHIP_AGG_KEEP_NULLS on these kinds, KHIP_AGG_K bits on any other kind.
+ * KHIP_E_UNSUPPORTED: SESSION windows, KHIP_FLAG_TABLE_SOURCE (Udaf, not TableUdaf: the reference
+ * rejects them there as it rejects MIN/MAX), a HAVING on the TOPK aggregate itself (a HAVING on
+ * another aggregate of the query is fine), and a k that needs more than the 29 state words of a
+ * row (k words per (kind, column, k), one more for TOPKDISTINCT of a BIGINT). */
+#define KHIP_AGG_TOPK 8
+#define KHIP_AGG_TOPKDISTINCT 9
+#define KHIP_AGG_K(k) ((int32_t)(k) << 16)
 
 /* Where a batch's column pointers live. */
 #define KHIP_MEM_HOST 0
@@ -217,7 +239,8 @@ typedef struct khip_having {
 } khip_having;
 
 typedef struct khip_agg_spec {
-  int32_t kind;    /* KHIP_AGG_* (the offset kinds: | KHIP_AGG_KEEP_NULLS)              */
+  int32_t kind;    /* KHIP_AGG_* (the offset kinds: | KHIP_AGG_KEEP_NULLS; the TOPK
+                      kinds: | KHIP_AGG_K(k))                                          */
   int32_t arg_col; /* value column index (ignored for COUNT_STAR)                     */
 } khip_agg_spec;
 
@@ -256,7 +279,15 @@ typedef struct khip_agg khip_agg;
 /* Final materialized table, sorted by (key, window_start).  Caller-allocated.
  * Row = [key, agg results..., WINDOWSTART, WINDOWEND]
  * (S/AggregateParamsFactory.java:156-190, S/StreamAggregateBuilder.java:355-373)
- * plus the row timestamp (max ROWTIME applied to the entry). */
+ * plus the row timestamp (max ROWTIME applied to the entry).
+ *
+ * ARRAY results (TOPK / TOPKDISTINCT: SqlArray.of(inputType), TopkKudaf.java:104-110).  Aggregate
+ * i has a result length L = khip_agg_result_len() (1 for every scalar aggregate, k for the two
+ * TOPK kinds) and an element type khip_agg_result_type().  agg_values[i] holds capacity x L
+ * elements and agg_null[i] capacity x L bytes, row-major: row r's list is the elements [r*L,
+ * r*L + len), in descending order, each with null byte 0; the slots [r*L + len, (r+1)*L) have null
+ * byte 1 and value 0.  len = 0 is the empty array, never SQL NULL.  With L = 1 this is the scalar
+ * layout.  khip_agg_snapshot, khip_agg_get and khip_agg_changes all write it. */
 typedef struct khip_snapshot {
   int64_t capacity;            /* rows the buffers below can hold                     */
   int64_t n_rows;              /* out                                                 */
@@ -268,8 +299,10 @@ typedef struct khip_snapshot {
   int64_t* window_start;       /* 0 for KHIP_WINDOW_NONE                              */
   int64_t* window_end;
   int64_t* rowtime;
-  void** agg_values;           /* per agg; element type from khip_agg_result_type()   */
-  uint8_t** agg_null;          /* per agg; 1 byte per row, 1 = SQL NULL               */
+  void** agg_values;           /* per agg; element type from khip_agg_result_type(),
+                                  capacity x khip_agg_result_len() elements            */
+  uint8_t** agg_null;          /* per agg; 1 byte per element, 1 = SQL NULL (array
+                                  results: 1 = past the end of the row's list)         */
 } khip_snapshot;
 
 /* KSPlanBuilder.visitStreamWindowedAggregate / visitStreamAggregate
@@ -282,6 +315,11 @@ khip_status khip_agg_create(const khip_agg_desc* desc, khip_agg** out);
  * MIN/MAX(T) → T, AVG → DOUBLE. */
 khip_status khip_agg_result_type(const khip_agg_desc* desc, int32_t agg_index,
                                  int32_t* out_type);
+
+/* Result length of aggregate i: 1 for a scalar aggregate, k for TOPK / TOPKDISTINCT (whose
+ * khip_agg_result_type is the ELEMENT type, the argument's).  Sizes khip_snapshot's arrays. */
+khip_status khip_agg_result_len(const khip_agg_desc* desc, int32_t agg_index,
+                                int32_t* out_len);
 
 /* Per-record KStreamWindowAggregate.process + KudafAggregator.apply
  * (X/function/udaf/KudafAggregator.java:56-80) over a whole micro-batch:

@@ -30,7 +30,13 @@ TYPE = {"INT32": 0, "INT64": 1, "DOUBLE": 2}
 AGG_KEEP_NULLS = 0x100  # KHIP_AGG_KEEP_NULLS: ignoreNulls = false, OR-ed into the two offset kinds
 AGG = {"COUNT_STAR": 0, "COUNT": 1, "SUM": 2, "MIN": 3, "MAX": 4, "AVG": 5,
        "LATEST_BY_OFFSET": 6, "EARLIEST_BY_OFFSET": 7,
-       "LATEST_BY_OFFSET_NULLS": 6 | AGG_KEEP_NULLS, "EARLIEST_BY_OFFSET_NULLS": 7 | AGG_KEEP_NULLS}
+       "LATEST_BY_OFFSET_NULLS": 6 | AGG_KEEP_NULLS, "EARLIEST_BY_OFFSET_NULLS": 7 | AGG_KEEP_NULLS,
+       "TOPK": 8, "TOPKDISTINCT": 9}
+
+
+def AGG_K(k):
+    """KHIP_AGG_K(k): the k of TOPK / TOPKDISTINCT, OR-ed into the aggregate kind."""
+    return int(k) << 16
 OP = {"GT": 0, "GE": 1, "LT": 2, "LE": 3, "EQ": 4, "NE": 5}
 JOIN = {"LEFT": 0, "INNER": 1}
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -201,6 +207,7 @@ SIGS = {
 }
 PRODUCT_ONLY = {
     "agg_result_type": ([C.POINTER(AggDesc), i32, C.POINTER(i32)]),
+    "agg_result_len": ([C.POINTER(AggDesc), i32, C.POINTER(i32)]),
     "agg_count_rows": ([_P, C.POINTER(Having), C.POINTER(i64)]),
     "agg_get": ([_P, C.POINTER(Pull), C.POINTER(Having), C.POINTER(Snapshot)]),
     "agg_reset": ([_P]),
@@ -368,9 +375,12 @@ def make_agg_desc(window_kind="NONE", key_type="INT64", size_ms=0, advance_ms=0,
                   col_types=(), aggs=(), device=0, capacity_hint=0, flags=0, retention_ms=RETENTION_DEFAULT,
                   emit="CHANGES", having=None, time_domain="TASK", n_partitions=0):
     """having: the query's HAVING ({"agg", "op", "value"}), maintained by the library (ABI 2).
-    time_domain / n_partitions: the stream-time domain (ABI 5; include/ksqldb_hip.h KHIP_TIME_*)."""
+    time_domain / n_partitions: the stream-time domain (ABI 5; include/ksqldb_hip.h KHIP_TIME_*).
+    aggs: (kind, column) per aggregate; TOPK / TOPKDISTINCT take their k as a third element,
+    ("TOPK", column, k)."""
     ct = (i32 * max(len(col_types), 1))(*[TYPE[t] if isinstance(t, str) else t for t in col_types])
-    sp = (AggSpec * max(len(aggs), 1))(*[AggSpec(AGG[k] if isinstance(k, str) else k, c) for k, c in aggs])
+    sp = (AggSpec * max(len(aggs), 1))(*[AggSpec((AGG[a[0]] if isinstance(a[0], str) else a[0]) |
+                                                 (AGG_K(a[2]) if len(a) > 2 else 0), a[1]) for a in aggs])
     d = AggDesc(WINDOW[window_kind] if isinstance(window_kind, str) else window_kind,
                 KEY[key_type] if isinstance(key_type, str) else key_type,
                 size_ms, advance_ms if advance_ms else size_ms, grace_ms, len(col_types), ct,
@@ -382,7 +392,19 @@ def make_agg_desc(window_kind="NONE", key_type="INT64", size_ms=0, advance_ms=0,
     return d
 
 
+def agg_is_array(kind):
+    """TOPK / TOPKDISTINCT (with their k bits): the result is an ARRAY."""
+    return (kind & 0xFFFF) in (AGG["TOPK"], AGG["TOPKDISTINCT"])
+
+
+def agg_result_len(desc):
+    """Per aggregate the result length L (khip_agg_result_len): 1 for a scalar aggregate, k for TOPK /
+    TOPKDISTINCT.  A snapshot holds capacity x L elements (and null bytes) per aggregate."""
+    return [max(desc.aggs[i].kind >> 16, 1) if agg_is_array(desc.aggs[i].kind) else 1 for i in range(desc.n_aggs)]
+
+
 def result_types(desc):
+    """Per aggregate the result's element type (khip_agg_result_type)."""
     out = []
     for i in range(desc.n_aggs):
         k = desc.aggs[i].kind
@@ -390,7 +412,7 @@ def result_types(desc):
             out.append(TYPE["INT64"])
         elif k == AGG["AVG"]:
             out.append(TYPE["DOUBLE"])
-        else:  # SUM / MIN / MAX, and LATEST / EARLIEST_BY_OFFSET (with or without AGG_KEEP_NULLS)
+        else:  # SUM / MIN / MAX, LATEST / EARLIEST_BY_OFFSET (with or without AGG_KEEP_NULLS), TOPK / TOPKDISTINCT
             out.append(desc.col_types[desc.aggs[i].arg_col])
     return out
 
@@ -536,13 +558,17 @@ class AggHandle:
             return out
 
     def _materialize_into(self, having, call, cap, kcap, raw_keys=False):
+        # array aggregates (TOPK / TOPKDISTINCT, L = k): values and nulls are (rows, L) arrays, row r's
+        # list its leading elements whose null flag is False, in descending order; scalars stay 1-D
         rt = result_types(self.desc)
+        rl = agg_result_len(self.desc)
+        arr = [agg_is_array(self.desc.aggs[i].kind) for i in range(len(rt))]
         arrays = {
             "key": np.zeros(cap, np.int64), "key_offsets": np.zeros(cap + 1, np.int64),
             "key_bytes": np.zeros(kcap, np.uint8), "ws": np.zeros(cap, np.int64),
             "we": np.zeros(cap, np.int64), "rowtime": np.zeros(cap, np.int64),
-            "values": [np.zeros(cap, NP_TYPE[t]) for t in rt],
-            "nulls": [np.zeros(cap, np.uint8) for _ in rt],
+            "values": [np.zeros((cap, L) if a else cap, NP_TYPE[t]) for t, L, a in zip(rt, rl, arr)],
+            "nulls": [np.zeros((cap, L) if a else cap, np.uint8) for L, a in zip(rl, arr)],
         }
         av = (C.c_void_p * max(len(rt), 1))(*[a.ctypes.data for a in arrays["values"]])
         an = (C.c_void_p * max(len(rt), 1))(*[a.ctypes.data for a in arrays["nulls"]])

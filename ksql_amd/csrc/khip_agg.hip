@@ -184,7 +184,7 @@ __device__ __forceinline__ int upsert_apply(const ApplyParams& p, uint64_t* __re
       __hip_atomic_fetch_max((int64_t*)&s[2], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       for (int o = 0; o < p.n_ops; o++) {
         const UpdOp op = p.ops[o];
-        int64_t* w = (int64_t*)&s[op.word];
+        int64_t* w = (int64_t*)&s[op_word(op)];
         if (op.kind == OP_INC) {
           __hip_atomic_fetch_add(w, (int64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           continue;
@@ -216,6 +216,29 @@ __device__ __forceinline__ int upsert_apply(const ApplyParams& p, uint64_t* __re
               __hip_atomic_fetch_min(w, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             else
               __hip_atomic_fetch_max(w, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            break;
+          }
+          case OP_TOPK:
+          case OP_TOPK_DISTINCT: {
+            // The insertion chain of k_part_agg's lds_apply (DESIGN.md "TOPK aggregates") on the
+            // slot's words in HBM: returning agent-scope max atomics (global_atomic_smax_x2), any
+            // interleaving with the other records of the group.  A record resumed after a table
+            // doubling restarts at its first unapplied window, so no chain runs twice.
+            int64_t v = load_col_raw(cols, ty, op.col, row);
+            if (ty == KHIP_TYPE_DOUBLE) {
+              double d;
+              __builtin_memcpy(&d, &v, 8);
+              v = f64_order_key(d);
+            }
+            const bool distinct = op.kind == OP_TOPK_DISTINCT;
+            const int ns = op_slots(op);
+            if (distinct && v == INT64_MIN)  // TOPKDISTINCT(BIGINT) Long.MIN_VALUE: the flag word
+              __hip_atomic_fetch_max(w + ns, (int64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int j = 0; j < ns && v != INT64_MIN; j++) {
+              const int64_t old = __hip_atomic_fetch_max(w + j, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              if (distinct && old == v) break;
+              v = old < v ? old : v;
+            }
             break;
           }
           default:
@@ -1134,7 +1157,12 @@ void dict_release(KeyDict& d) {
 
 using namespace khip;
 
-static inline int agg_base_kind(int32_t kind) { return kind & ~KHIP_AGG_KEEP_NULLS; }
+static inline int agg_base_kind(int32_t kind) { return kind & 0xFFFF & ~KHIP_AGG_KEEP_NULLS; }  // without flag / k bits
+static inline int agg_k_bits(int32_t kind) { return kind >> 16; }  // KHIP_AGG_K(k), signed
+static inline bool agg_is_topk(int32_t kind) {
+  const int b = agg_base_kind(kind);
+  return b == KHIP_AGG_TOPK || b == KHIP_AGG_TOPKDISTINCT;
+}
 static inline bool agg_is_offset(int32_t kind) {
   const int b = agg_base_kind(kind);
   return b == KHIP_AGG_LATEST_BY_OFFSET || b == KHIP_AGG_EARLIEST_BY_OFFSET;
@@ -1185,6 +1213,10 @@ static khip_status plan_state(khip_agg* a) {
       continue;
     }
     const int c = s.arg_col;
+    if (agg_is_topk(s.kind)) {  // TOPK's length is min(the column's non-null count, k); its slots: below
+      if (s.kind == KHIP_AGG_TOPK && w_cnt[c] < 0) w_cnt[c] = word++;
+      continue;
+    }
     // the column's non-null count: COUNT(col), AVG's divisor, MIN/MAX's null test.  SUM alone needs
     // none (SUM over only NULLs is 0, SumKudaf's initial value): its rows stay 32 bytes
     if (s.kind != KHIP_AGG_SUM && w_cnt[c] < 0) w_cnt[c] = word++;
@@ -1199,6 +1231,31 @@ static khip_status plan_state(khip_agg* a) {
     int& w = latest ? w_max[h] : w_min[h];
     if (w < 0) w = word++;
     a->offs.a[a->out_off[i]].w_seq = (int16_t)w;
+  }
+  // TOPK / TOPKDISTINCT: per (kind, column, k) k consecutive words of order keys, sorted descending,
+  // INT64_MIN = empty; TOPKDISTINCT over BIGINT one more, "Long.MIN_VALUE seen" (that value's key is
+  // the empty slot's, so it never enters the slots)
+  struct TopkSpan { int kind, col, k, word; };
+  std::vector<TopkSpan> spans;
+  std::vector<int> out_span(d.n_aggs, -1);
+  a->out_flag.assign(d.n_aggs, -1);
+  a->has_topk = false;
+  for (int i = 0; i < d.n_aggs; i++) {
+    const khip_agg_spec& s = a->aggs[i];
+    if (!agg_is_topk(s.kind)) continue;
+    a->has_topk = true;
+    const int k = a->agg_k[i];
+    for (size_t j = 0; j < spans.size(); j++)
+      if (spans[j].kind == s.kind && spans[j].col == s.arg_col && spans[j].k == k) out_span[i] = (int)j;
+    if (out_span[i] < 0) {
+      const bool flag = s.kind == KHIP_AGG_TOPKDISTINCT && a->col_types[s.arg_col] == KHIP_TYPE_INT64;
+      if (word + k + (flag ? 1 : 0) > 32) return fail(KHIP_E_UNSUPPORTED, "too many aggregate state words (max 29)");
+      out_span[i] = (int)spans.size();
+      spans.push_back(TopkSpan{s.kind, s.arg_col, k, word});
+      word += k + (flag ? 1 : 0);
+    }
+    const TopkSpan& sp = spans[out_span[i]];
+    if (s.kind == KHIP_AGG_TOPKDISTINCT && a->col_types[s.arg_col] == KHIP_TYPE_INT64) a->out_flag[i] = sp.word + sp.k;
   }
   if (word > 32) return fail(KHIP_E_UNSUPPORTED, "too many aggregate state words (max 29)");
   a->sw = (int)next_pow2(std::max(word, 4));
@@ -1224,6 +1281,8 @@ static khip_status plan_state(khip_agg* a) {
     if (w_min[c] >= 0) add(OP_MIN, c, w_min[c]);
     if (w_max[c] >= 0) add(OP_MAX, c, w_max[c]);
   }
+  for (const TopkSpan& sp : spans)  // (op_word / op_slots)
+    add(sp.kind == KHIP_AGG_TOPK ? OP_TOPK : OP_TOPK_DISTINCT, sp.col, sp.word | (sp.k << 8));
   p.n_ops = n;
   for (int w = 0; w < 32; w++) a->init.w[w] = 0;
   a->init.w[1] = EMPTY_WS;
@@ -1232,6 +1291,8 @@ static khip_status plan_state(khip_agg* a) {
     if (w_min[c] >= 0) a->init.w[w_min[c]] = INT64_MAX;
     if (w_max[c] >= 0) a->init.w[w_max[c]] = INT64_MIN;
   }
+  for (const TopkSpan& sp : spans)  // (the flag word stays 0)
+    for (int j = 0; j < sp.k; j++) a->init.w[sp.word + j] = INT64_MIN;
   a->outs.clear();
   for (int i = 0; i < d.n_aggs; i++) {
     const khip_agg_spec& s = a->aggs[i];
@@ -1248,6 +1309,11 @@ static khip_status plan_state(khip_agg* a) {
       case KHIP_AGG_MAX: o.w_val = w_max[s.arg_col]; break;
       case KHIP_AGG_LATEST_BY_OFFSET:
       case KHIP_AGG_EARLIEST_BY_OFFSET: o.w_val = a->offs.a[a->out_off[i]].w_val; break;  // (decoded by emit_snapshot)
+      case KHIP_AGG_TOPK:
+      case KHIP_AGG_TOPKDISTINCT:  // the first slot word (decoded by emit_snapshot); TOPKDISTINCT has no count
+        o.w_val = spans[out_span[i]].word;
+        if (o.kind == KHIP_AGG_TOPKDISTINCT) o.w_cnt = -1;
+        break;
     }
     a->outs.push_back(o);
   }
@@ -1387,7 +1453,14 @@ khip_status khip_agg_result_type(const khip_agg_desc* d, int32_t i, int32_t* out
   const khip_agg_spec& s = d->aggs[i];
   if (s.kind == KHIP_AGG_COUNT_STAR || s.kind == KHIP_AGG_COUNT) *out = KHIP_TYPE_INT64;
   else if (s.kind == KHIP_AGG_AVG) *out = KHIP_TYPE_DOUBLE;
-  else *out = d->col_types[s.arg_col];
+  else *out = d->col_types[s.arg_col];  // (TOPK / TOPKDISTINCT: the element type)
+  return KHIP_OK;
+}
+
+khip_status khip_agg_result_len(const khip_agg_desc* d, int32_t i, int32_t* out) {
+  if (!d || !out || i < 0 || i >= d->n_aggs) return fail(KHIP_E_INVALID, "bad aggregate index");
+  const khip_agg_spec& s = d->aggs[i];
+  *out = agg_is_topk(s.kind) ? std::max(agg_k_bits(s.kind), 1) : 1;
   return KHIP_OK;
 }
 
@@ -1408,16 +1481,30 @@ khip_status khip_agg_create(const khip_agg_desc* desc, khip_agg** out) {
   for (int c = 0; c < d.n_cols; c++)
     if (d.col_types[c] < KHIP_TYPE_INT32 || d.col_types[c] > KHIP_TYPE_DOUBLE)
       return fail(KHIP_E_INVALID, "column type");
-  bool has_offset = false;
+  bool has_offset = false, has_topk = false;
   for (int i = 0; i < d.n_aggs; i++) {
     const khip_agg_spec& s = d.aggs[i];
     const int bk = agg_base_kind(s.kind);
-    if (bk < KHIP_AGG_COUNT_STAR || bk > KHIP_AGG_EARLIEST_BY_OFFSET) return fail(KHIP_E_INVALID, "aggregate kind");
+    if (bk < KHIP_AGG_COUNT_STAR || bk > KHIP_AGG_TOPKDISTINCT) return fail(KHIP_E_INVALID, "aggregate kind");
     if ((s.kind & KHIP_AGG_KEEP_NULLS) && !agg_is_offset(s.kind))
       return fail(KHIP_E_INVALID, "KHIP_AGG_KEEP_NULLS on an aggregate other than LATEST / EARLIEST_BY_OFFSET");
-    if (s.kind != KHIP_AGG_COUNT_STAR && (s.arg_col < 0 || s.arg_col >= d.n_cols))
+    if (agg_is_topk(s.kind) ? agg_k_bits(s.kind) < 1 : agg_k_bits(s.kind) != 0)
+      return fail(KHIP_E_INVALID, agg_is_topk(s.kind) ? "TOPK / TOPKDISTINCT: k (KHIP_AGG_K) must be at least 1"
+                                                      : "KHIP_AGG_K on an aggregate other than TOPK / TOPKDISTINCT");
+    if (bk != KHIP_AGG_COUNT_STAR && (s.arg_col < 0 || s.arg_col >= d.n_cols))
       return fail(KHIP_E_INVALID, "aggregate argument column");
     has_offset = has_offset || agg_is_offset(s.kind);
+    has_topk = has_topk || agg_is_topk(s.kind);
+  }
+  if (has_topk) {
+    // merged list by list (TopkKudaf.merge) in the reference: not on the device
+    if (d.window_kind == KHIP_WINDOW_SESSION) return fail(KHIP_E_UNSUPPORTED, "TOPK / TOPKDISTINCT with SESSION windows");
+    // Udafs, not TableUdafs (no undo): the reference rejects them on a table source as it rejects MIN/MAX
+    if (d.flags & KHIP_FLAG_TABLE_SOURCE)
+      return fail(KHIP_E_UNSUPPORTED, "TOPK / TOPKDISTINCT cannot be applied to a table source");
+    if (d.has_having && d.having.agg_index >= 0 && d.having.agg_index < d.n_aggs &&
+        agg_is_topk(d.aggs[d.having.agg_index].kind))
+      return fail(KHIP_E_UNSUPPORTED, "HAVING on a TOPK / TOPKDISTINCT aggregate (an ARRAY)");
   }
   if (has_offset) {
     // merged by sequence (Udaf.merge) in the reference: not on the device
@@ -1465,6 +1552,11 @@ khip_status khip_agg_create(const khip_agg_desc* desc, khip_agg** out) {
   a->desc = d;
   a->col_types.assign(d.col_types, d.col_types + d.n_cols);
   a->aggs.assign(d.aggs, d.aggs + d.n_aggs);
+  a->agg_k.assign(d.n_aggs, 0);
+  for (int i = 0; i < d.n_aggs; i++) {  // the handle's specs keep the bare kind (and KEEP_NULLS); k apart
+    a->agg_k[i] = agg_k_bits(a->aggs[i].kind);
+    a->aggs[i].kind &= 0xFFFF;
+  }
   a->desc.col_types = a->col_types.data();
   a->desc.aggs = a->aggs.data();
   if (d.window_kind == KHIP_WINDOW_TUMBLING || d.window_kind == KHIP_WINDOW_SESSION) a->desc.advance_ms = d.size_ms;
@@ -2192,6 +2284,8 @@ static khip_status compact_rows(khip_agg* a, const khip_having* h, std::vector<u
     if (h->op < KHIP_OP_GT || h->op > KHIP_OP_NE) return fail(KHIP_E_INVALID, "having op");
     if (agg_is_offset(a->aggs[h->agg_index].kind))  // (decode_words does not know the offset kinds)
       return fail(KHIP_E_UNSUPPORTED, "HAVING on a LATEST / EARLIEST_BY_OFFSET aggregate");
+    if (agg_is_topk(a->aggs[h->agg_index].kind))  // (nor the TOPK kinds: an ARRAY has no comparison)
+      return fail(KHIP_E_UNSUPPORTED, "HAVING on a TOPK / TOPKDISTINCT aggregate (an ARRAY)");
     hd.active = 1;
     hd.op = h->op;
     hd.a = a->outs[h->agg_index];
@@ -2353,6 +2447,30 @@ static khip_status emit_snapshot(khip_agg* a, const std::vector<uint64_t>& rows,
     if (out->rowtime) out->rowtime[r] = (int64_t)s[2];
     for (int i = 0; i < a->desc.n_aggs; i++) {
       const AggOut& o = a->outs[i];
+      if (o.kind == KHIP_AGG_TOPK || o.kind == KHIP_AGG_TOPKDISTINCT) {
+        // the ARRAY layout of khip_snapshot: L = k elements per row, the list first (descending:
+        // the slots' order), then null slots.  TOPK: the column's non-null count says how many
+        // slots are values (a Long.MIN_VALUE has the empty slot's key); TOPKDISTINCT: the leading
+        // slots that are not empty, then Long.MIN_VALUE if its flag word is set and there is room.
+        const int L = a->agg_k[i];
+        int len = 0;
+        if (o.kind == KHIP_AGG_TOPK) len = (int)std::min<int64_t>((int64_t)s[o.w_cnt], L);
+        else
+          while (len < L && (int64_t)s[o.w_val + len] != INT64_MIN) len++;
+        const bool tail_min = a->out_flag[i] >= 0 && s[a->out_flag[i]] != 0 && len < L;
+        for (int j = 0; j < L; j++) {
+          const bool has = j < len || (tail_min && j == len);
+          const int64_t key = j < len ? (int64_t)s[o.w_val + j] : INT64_MIN;
+          const int64_t at = r * L + j;
+          if (out->agg_values && out->agg_values[i]) {
+            if (o.type == KHIP_TYPE_INT32) ((int32_t*)out->agg_values[i])[at] = has ? (int32_t)key : 0;
+            else if (o.type == KHIP_TYPE_INT64) ((int64_t*)out->agg_values[i])[at] = has ? key : 0;
+            else ((double*)out->agg_values[i])[at] = has ? f64_from_order_key(key) : 0.0;
+          }
+          if (out->agg_null && out->agg_null[i]) out->agg_null[i][at] = has ? 0 : 1;
+        }
+        continue;
+      }
       int64_t iv = 0;
       double dv = 0.0;
       bool isnull = false;

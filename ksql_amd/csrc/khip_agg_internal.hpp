@@ -20,13 +20,21 @@ constexpr int NPART = 8;
 
 enum { P_ACCEPTED, P_NULL_KEY, P_NULL_ROW, P_BAD_TS, P_APPLIED, P_LATE, P_FAILED, P_NEW };
 
-enum OpKind : int8_t { OP_INC = 0, OP_INC_VALID, OP_ADD_I64, OP_ADD_F64, OP_MIN, OP_MAX };
+// OP_TOPK / OP_TOPK_DISTINCT (TOPK / TOPKDISTINCT, "TOPK aggregates" in DESIGN.md): op_slots(op)
+// consecutive state words from op_word(op) hold order keys sorted descending, INT64_MIN = empty;
+// a record's key is inserted by the chain in lds_apply / upsert_apply.  Only k_part_agg and k_apply
+// know the two kinds: a handle with one takes no other aggregate kernel.
+enum OpKind : int8_t { OP_INC = 0, OP_INC_VALID, OP_ADD_I64, OP_ADD_F64, OP_MIN, OP_MAX, OP_TOPK, OP_TOPK_DISTINCT };
 
 struct UpdOp {
   int8_t kind;
   int8_t col;
-  int16_t word;
+  int16_t word;  // the state word; the TOPK kinds: first slot word | slots << 8 (state words are < 32)
 };
+// (the slot count shares `word` so that the struct, and with it the parameter blocks and the code of
+// every kernel that never sees a TOPK op, stay what they were)
+__host__ __device__ __forceinline__ int op_word(const UpdOp& o) { return o.word & 0xFF; }
+__host__ __device__ __forceinline__ int op_slots(const UpdOp& o) { return (o.word >> 8) & 0xFF; }
 
 struct ApplyParams {
   int32_t windowed;
@@ -37,6 +45,13 @@ struct ApplyParams {
   int32_t col_type[MAX_COLS];
   UpdOp ops[MAX_OPS];
 };
+
+// State words an op owns from op_word(): 1, or a TOPK op's slots (+ the "Long.MIN_VALUE seen" flag
+// word of a TOPKDISTINCT over BIGINT, whose key is the empty slot's).
+inline int op_span(const ApplyParams& p, const UpdOp& o) {
+  if (o.kind != OP_TOPK && o.kind != OP_TOPK_DISTINCT) return 1;
+  return op_slots(o) + (o.kind == OP_TOPK_DISTINCT && p.col_type[o.col] == KHIP_TYPE_INT64 ? 1 : 0);
+}
 
 struct ColPtrs {
   const void* data[MAX_COLS];
@@ -630,6 +645,11 @@ struct khip_agg {
   int hid_src[MAX_COLS] = {};
   DevBuf seqbuf;
   int64_t seq_base = 0;  // rows pushed since the handle's creation or last reset
+  // ---- TOPK / TOPKDISTINCT: aggs[i].kind holds the bare kind (the caller's KHIP_AGG_K bits are
+  // agg_k[i], 0 for a scalar aggregate); out_flag[i]: the TOPKDISTINCT(BIGINT) flag word, or -1.
+  // has_topk: only k_part_agg / k_apply run this handle's records (part_push: merge_allow).
+  std::vector<int> agg_k, out_flag;
+  bool has_topk = false;
   int sw = 4;
   // table
   DevBuf table;

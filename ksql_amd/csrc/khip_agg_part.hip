@@ -1378,7 +1378,7 @@ __device__ __forceinline__ void lds_apply(const PartAggParams& q, lds_i64* lw, i
   __hip_atomic_fetch_max(&lw[2 * H + e], t, WG_RLX);
   for (int o = 0; o < q.n_ops; o++) {
     const UpdOp op = q.ops[o];
-    lds_i64* w = &lw[op.word * H + e];
+    lds_i64* w = &lw[op_word(op) * H + e];
     if (op.kind == OP_INC) {
       __hip_atomic_fetch_add(w, (int64_t)1, WG_RLX);
       continue;
@@ -1405,6 +1405,30 @@ __device__ __forceinline__ void lds_apply(const PartAggParams& q, lds_i64* lw, i
         }
         if (op.kind == OP_MIN) __hip_atomic_fetch_min(w, k, WG_RLX);
         else __hip_atomic_fetch_max(w, k, WG_RLX);
+        break;
+      }
+      case OP_TOPK:
+      case OP_TOPK_DISTINCT: {
+        // The insertion chain (DESIGN.md "TOPK aggregates"): the key enters at slot 0; what a slot's
+        // max does not keep moves on to the next.  Single-word returning LDS max atomics
+        // (ds_max_rtn_i64), so the lanes of every wave may run their chains on one entry in any
+        // interleaving.  The entry's slots start as the resident row's (or INT64_MIN = empty).
+        int64_t v = raw;
+        if (q.col_type[op.col] == KHIP_TYPE_DOUBLE) {
+          double d;
+          __builtin_memcpy(&d, &raw, 8);
+          v = f64_order_key(d);
+        }
+        const bool distinct = op.kind == OP_TOPK_DISTINCT;
+        const int ns = op_slots(op);
+        // TOPKDISTINCT(BIGINT): Long.MIN_VALUE is the empty slot's key, so it is a flag word after
+        // the slots instead (no other type has a value with that key)
+        if (distinct && v == INT64_MIN) __hip_atomic_fetch_max(w + ns * H, (int64_t)1, WG_RLX);
+        for (int j = 0; j < ns && v != INT64_MIN; j++) {
+          const int64_t old = __hip_atomic_fetch_max(w + j * H, v, WG_RLX);
+          if (distinct && old == v) break;  // a copy is resident: drop this one
+          v = old < v ? old : v;            // what did not stay in slot j
+        }
         break;
       }
       default: break;
@@ -3479,7 +3503,8 @@ khip_status part_init(khip_agg* a, int64_t hint) {
   (void)nwords;
   // words used = highest word index + 1 (rows are padded to a->sw)
   int used = 3;
-  for (int o = 0; o < a->ap.n_ops; o++) used = std::max(used, a->ap.ops[o].word + 1);
+  for (int o = 0; o < a->ap.n_ops; o++)  // (a TOPK op: its whole slot span)
+    used = std::max(used, op_word(a->ap.ops[o]) + op_span(a->ap, a->ap.ops[o]));
   s.nwords = used;
   const int entry = 4 + 8 * used;
   // LDS table: the largest power of two within the budget (default 80 KB: two workgroups
@@ -3523,7 +3548,7 @@ khip_status part_init(khip_agg* a, int64_t hint) {
     off += (mH * 2 + 15) & ~15;
     s.m_lds = off;
     for (int w = 0; w < 32; w++) s.word_op[w] = -1;
-    for (int o = 0; o < a->ap.n_ops; o++) s.word_op[a->ap.ops[o].word] = (int8_t)o;
+    for (int o = 0; o < a->ap.n_ops; o++) s.word_op[op_word(a->ap.ops[o])] = (int8_t)o;
     if (mH >= 256) s.H_eff = std::min(s.H_eff, mH * 3 / 4);
   }
   // partitions: at most ~H_eff/2 groups each at the hinted size
@@ -3937,7 +3962,8 @@ khip_status part_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t
   KHIP_TRY(s.wr.ensure(128));
   KHIP_TRY(s.res.ensure(16));
   KHIP_TRY(s.closed_ctr.ensure(8));
-  const bool merge_allow = s.mH >= 256 && knob("KHIP_MERGE", 1) != 0;
+  // (a TOPK / TOPKDISTINCT handle: k_part_agg only — the merges have no plane form of the chain)
+  const bool merge_allow = s.mH >= 256 && knob("KHIP_MERGE", 1) != 0 && !a->has_topk;
   // which merge kernel pass 0 runs (host-known): the lean COUNT(*) merge reads R8 records too
   const bool narrow = s.rw == 2;
   const int64_t r12_mode = knob("KHIP_R12", 1);  // 1: 12-byte records end to end; 2: pass A only

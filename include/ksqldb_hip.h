@@ -48,7 +48,9 @@ typedef int32_t khip_status;
                                    windows, KHIP_FLAG_TABLE_SOURCE, a HAVING on the offset
                                    aggregate itself, more user + hidden sequence columns
                                    than 8, and khip_agg_push_shuffled on such a handle; the
-                                   N forms (arrays) are never routed here.
+                                   N forms (col, N) besides: an N whose value and slot words
+                                   exceed the 29 state words (their SESSION merge is not on
+                                   the device either).
                                    TOPK / TOPKDISTINCT: the struct form topk(col, other...,
                                    k), a STRING / DECIMAL / DATE / TIME / TIMESTAMP / BYTES
                                    argument (never routed here), SESSION windows,
@@ -98,7 +100,22 @@ typedef int32_t khip_status;
  * whose argument is not NULL; with KHIP_AGG_KEEP_NULLS (ignoreNulls = false) the argument of the
  * last / first record, NULL included.  The result has the argument's type and its exact bits (a
  * DOUBLE keeps its NaN payload and -0.0).  Not with SESSION windows, KHIP_FLAG_TABLE_SOURCE, as
- * the HAVING aggregate, or through khip_agg_push_shuffled: KHIP_E_UNSUPPORTED. */
+ * the HAVING aggregate, or through khip_agg_push_shuffled: KHIP_E_UNSUPPORTED.
+ *
+ * The N forms LATEST_BY_OFFSET(col, N[, ignoreNulls]) / EARLIEST_BY_OFFSET(col, N[, ignoreNulls]):
+ * LatestByOffset.java:149-218 (latestTN), EarliestByOffset.java:162-228 (earliestTN).  The literal
+ * N >= 1 is OR-ed into khip_agg_spec.kind with KHIP_AGG_K(N), with KHIP_AGG_KEEP_NULLS for
+ * ignoreNulls = false; no KHIP_AGG_K bits is the scalar form above, N = 1 an array of at most one
+ * element.  The result is an ARRAY of the argument's type: the group's last / first N records in
+ * arrival order, oldest first, fewer while the group has seen fewer, [] (never SQL NULL) for a
+ * group with no such record.  Records with a NULL argument are skipped; with KHIP_AGG_KEEP_NULLS
+ * they are records like any other and give NULL elements.  Elements keep the argument's exact
+ * bits.  khip_agg_result_len is N, khip_agg_result_type the argument's type; the layout in a
+ * khip_snapshot: see khip_snapshot below.  KHIP_E_INVALID: negative KHIP_AGG_K bits (N <= 0 is a
+ * plan-time error of the reference).  KHIP_E_UNSUPPORTED: as for the scalar forms, and an N that
+ * needs more than the 29 state words of a row (per aggregate N value words, one null-mask word
+ * with KHIP_AGG_KEEP_NULLS, one more for LATEST; N slot words per (function, null handling,
+ * column, N)).  Their merge (SESSION windows) is not on the device. */
 #define KHIP_AGG_LATEST_BY_OFFSET 6
 #define KHIP_AGG_EARLIEST_BY_OFFSET 7
 /* OR-ed into khip_agg_spec.kind of the two kinds above: ignoreNulls = false */
@@ -112,7 +129,8 @@ typedef int32_t khip_status;
  * duplicates (the multiset top k); TOPKDISTINCT keeps one copy per value, equality being equals():
  * for DOUBLE every NaN is one value (returned as the canonical NaN, above +Infinity) and -0.0 is
  * not 0.0.  How the array is laid out in a khip_snapshot: see khip_snapshot below.
- * KHIP_E_INVALID: k < 1, KHIP_AGG_KEEP_NULLS on these kinds, KHIP_AGG_K bits on any other kind.
+ * KHIP_E_INVALID: k < 1, KHIP_AGG_KEEP_NULLS on these kinds, KHIP_AGG_K bits on any other kind but
+ * the two offset kinds.
  * KHIP_E_UNSUPPORTED: SESSION windows, KHIP_FLAG_TABLE_SOURCE (Udaf, not TableUdaf: the reference
  * rejects them there as it rejects MIN/MAX), a HAVING on the TOPK aggregate itself (a HAVING on
  * another aggregate of the query is fine), and a k that needs more than the 29 state words of a
@@ -239,8 +257,9 @@ typedef struct khip_having {
 } khip_having;
 
 typedef struct khip_agg_spec {
-  int32_t kind;    /* KHIP_AGG_* (the offset kinds: | KHIP_AGG_KEEP_NULLS; the TOPK
-                      kinds: | KHIP_AGG_K(k))                                          */
+  int32_t kind;    /* KHIP_AGG_* (the offset kinds: | KHIP_AGG_KEEP_NULLS, and
+                      | KHIP_AGG_K(N) for their N forms; the TOPK kinds:
+                      | KHIP_AGG_K(k))                                                 */
   int32_t arg_col; /* value column index (ignored for COUNT_STAR)                     */
 } khip_agg_spec;
 
@@ -287,7 +306,12 @@ typedef struct khip_agg khip_agg;
  * elements and agg_null[i] capacity x L bytes, row-major: row r's list is the elements [r*L,
  * r*L + len), in descending order, each with null byte 0; the slots [r*L + len, (r+1)*L) have null
  * byte 1 and value 0.  len = 0 is the empty array, never SQL NULL.  With L = 1 this is the scalar
- * layout.  khip_agg_snapshot, khip_agg_get and khip_agg_changes all write it. */
+ * layout.  khip_agg_snapshot, khip_agg_get and khip_agg_changes all write it.
+ *
+ * LATEST_BY_OFFSET(col, N) / EARLIEST_BY_OFFSET(col, N) use the same layout with L = N, the list
+ * oldest record first.  Their KHIP_AGG_KEEP_NULLS forms alone write a third null byte: 2 = a NULL
+ * element inside the list (value 0), which counts towards len; 0 (present) and 1 (past the end)
+ * keep their meaning. */
 typedef struct khip_snapshot {
   int64_t capacity;            /* rows the buffers below can hold                     */
   int64_t n_rows;              /* out                                                 */
@@ -302,7 +326,8 @@ typedef struct khip_snapshot {
   void** agg_values;           /* per agg; element type from khip_agg_result_type(),
                                   capacity x khip_agg_result_len() elements            */
   uint8_t** agg_null;          /* per agg; 1 byte per element, 1 = SQL NULL (array
-                                  results: 1 = past the end of the row's list)         */
+                                  results: 1 = past the end of the row's list, 2 = a
+                                  NULL element inside it)                              */
 } khip_snapshot;
 
 /* KSPlanBuilder.visitStreamWindowedAggregate / visitStreamAggregate
@@ -316,8 +341,9 @@ khip_status khip_agg_create(const khip_agg_desc* desc, khip_agg** out);
 khip_status khip_agg_result_type(const khip_agg_desc* desc, int32_t agg_index,
                                  int32_t* out_type);
 
-/* Result length of aggregate i: 1 for a scalar aggregate, k for TOPK / TOPKDISTINCT (whose
- * khip_agg_result_type is the ELEMENT type, the argument's).  Sizes khip_snapshot's arrays. */
+/* Result length of aggregate i: 1 for a scalar aggregate, k for TOPK / TOPKDISTINCT and N for the
+ * N forms of LATEST / EARLIEST_BY_OFFSET (whose khip_agg_result_type is the ELEMENT type, the
+ * argument's).  Sizes khip_snapshot's arrays. */
 khip_status khip_agg_result_len(const khip_agg_desc* desc, int32_t agg_index,
                                 int32_t* out_len);
 

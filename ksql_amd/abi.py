@@ -377,7 +377,7 @@ def make_agg_desc(window_kind="NONE", key_type="INT64", size_ms=0, advance_ms=0,
     """having: the query's HAVING ({"agg", "op", "value"}), maintained by the library (ABI 2).
     time_domain / n_partitions: the stream-time domain (ABI 5; include/ksqldb_hip.h KHIP_TIME_*).
     aggs: (kind, column) per aggregate; TOPK / TOPKDISTINCT take their k as a third element,
-    ("TOPK", column, k)."""
+    ("TOPK", column, k), and so do the N forms of the offset aggregates, ("LATEST_BY_OFFSET", column, N)."""
     ct = (i32 * max(len(col_types), 1))(*[TYPE[t] if isinstance(t, str) else t for t in col_types])
     sp = (AggSpec * max(len(aggs), 1))(*[AggSpec((AGG[a[0]] if isinstance(a[0], str) else a[0]) |
                                                  (AGG_K(a[2]) if len(a) > 2 else 0), a[1]) for a in aggs])
@@ -393,14 +393,35 @@ def make_agg_desc(window_kind="NONE", key_type="INT64", size_ms=0, advance_ms=0,
 
 
 def agg_is_array(kind):
-    """TOPK / TOPKDISTINCT (with their k bits): the result is an ARRAY."""
-    return (kind & 0xFFFF) in (AGG["TOPK"], AGG["TOPKDISTINCT"])
+    """TOPK / TOPKDISTINCT (with their k bits), and the N forms of LATEST / EARLIEST_BY_OFFSET (k bits
+    N >= 1; without k bits they are the scalar forms): the result is an ARRAY."""
+    base = kind & 0xFFFF & ~AGG_KEEP_NULLS
+    if base in (AGG["TOPK"], AGG["TOPKDISTINCT"]):
+        return True
+    return base in (AGG["LATEST_BY_OFFSET"], AGG["EARLIEST_BY_OFFSET"]) and (kind >> 16) >= 1
 
 
 def agg_result_len(desc):
     """Per aggregate the result length L (khip_agg_result_len): 1 for a scalar aggregate, k for TOPK /
-    TOPKDISTINCT.  A snapshot holds capacity x L elements (and null bytes) per aggregate."""
+    TOPKDISTINCT, N for LATEST / EARLIEST_BY_OFFSET(col, N).  A snapshot holds capacity x L elements
+    (and null bytes) per aggregate."""
     return [max(desc.aggs[i].kind >> 16, 1) if agg_is_array(desc.aggs[i].kind) else 1 for i in range(desc.n_aggs)]
+
+
+# khip_snapshot's null bytes of an array aggregate: an element, one past the list's end, and (the
+# KEEP_NULLS N forms of the offset aggregates only) a NULL element inside the list
+NULL_PRESENT, NULL_PAST_END, NULL_ELEMENT = 0, 1, 2
+
+
+def array_row(values, null_bytes, r):
+    """Row r of an array aggregate (values[i], null_bytes[i] of a snapshot / changes / get result) as a
+    Python list, oldest first for the offset aggregates' N forms, with None for a NULL element."""
+    out = []
+    for v, nb in zip(values[r], null_bytes[r]):
+        if nb == NULL_PAST_END:
+            break
+        out.append(None if nb == NULL_ELEMENT else v.item())
+    return out
 
 
 def result_types(desc):
@@ -412,7 +433,8 @@ def result_types(desc):
             out.append(TYPE["INT64"])
         elif k == AGG["AVG"]:
             out.append(TYPE["DOUBLE"])
-        else:  # SUM / MIN / MAX, LATEST / EARLIEST_BY_OFFSET (with or without AGG_KEEP_NULLS), TOPK / TOPKDISTINCT
+        else:  # SUM / MIN / MAX, LATEST / EARLIEST_BY_OFFSET (scalar and N forms, with or without AGG_KEEP_NULLS),
+            # TOPK / TOPKDISTINCT
             out.append(desc.col_types[desc.aggs[i].arg_col])
     return out
 
@@ -559,7 +581,10 @@ class AggHandle:
 
     def _materialize_into(self, having, call, cap, kcap, raw_keys=False):
         # array aggregates (TOPK / TOPKDISTINCT, L = k): values and nulls are (rows, L) arrays, row r's
-        # list its leading elements whose null flag is False, in descending order; scalars stay 1-D
+        # list its leading elements whose null flag is False, in descending order; scalars stay 1-D.
+        # "null_bytes" are the library's bytes as written (NULL_PRESENT / NULL_PAST_END / NULL_ELEMENT:
+        # the N forms of the offset aggregates have NULL elements inside a list, which "nulls" cannot tell
+        # from the list's end; array_row() reads them)
         rt = result_types(self.desc)
         rl = agg_result_len(self.desc)
         arr = [agg_is_array(self.desc.aggs[i].kind) for i in range(len(rt))]
@@ -584,7 +609,8 @@ class AggHandle:
             return None, st, s.n_rows
         m = s.n_rows
         out = {"n": m, "ws": arrays["ws"][:m], "we": arrays["we"][:m], "rowtime": arrays["rowtime"][:m],
-               "values": [v[:m] for v in arrays["values"]], "nulls": [v[:m].astype(bool) for v in arrays["nulls"]]}
+               "values": [v[:m] for v in arrays["values"]], "nulls": [v[:m].astype(bool) for v in arrays["nulls"]],
+               "null_bytes": [v[:m] for v in arrays["nulls"]]}
         if self.desc.key_type == KEY["UTF8"] and raw_keys:
             out["key_offsets"] = arrays["key_offsets"][: m + 1]
             out["key_bytes"] = arrays["key_bytes"][: int(arrays["key_offsets"][m]) if m else 0]

@@ -440,15 +440,26 @@ __global__ __launch_bounds__(256) void k_compact(const uint64_t* __restrict__ ta
 // it applies the records; a resolve kernel then turns the sequence words won by this push into
 // values, before anything reads the rows.  Groups won by earlier pushes are left alone, which keeps
 // EARLIEST stable and LATEST independent of how the stream is cut into pushes.
+// The N forms (col, N) keep the N largest keys of a hidden column with the TOPK chain (sequence for
+// LATEST, complemented sequence for EARLIEST) and the same resolve kernels bring the N values along
+// (off_resolve_list; DESIGN.md "Offset aggregates, N forms").
 
 __global__ __launch_bounds__(256) void k_off_iota(int64_t* __restrict__ seq, int64_t n, int64_t base) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     seq[i] = base + i;
 }
 
+// The complemented sequence column of EARLIEST's N forms: the N largest ~seq are the N smallest
+// sequences, oldest first.  ~seq is never INT64_MIN, the empty slot's key.
+__global__ __launch_bounds__(256) void k_off_iota_not(int64_t* __restrict__ nseq, int64_t n, int64_t base) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    nseq[i] = ~(base + i);
+}
+
 // Partitioned engine: a block per partition; only partitions the push's records reached are read
 // (k_part_chg's test: prn after a pipeline push, else the scatter's partition bases), the rows of
 // their current buffer.
+template <bool LISTS>
 __global__ __launch_bounds__(256) void k_off_resolve_part(uint64_t* __restrict__ b0, uint64_t* __restrict__ b1,
                                                           const uint8_t* __restrict__ sel,
                                                           const int64_t* __restrict__ cnt, int64_t cmax, int sw,
@@ -458,19 +469,21 @@ __global__ __launch_bounds__(256) void k_off_resolve_part(uint64_t* __restrict__
   if (prn ? prn[p] == 0 : pbase[p + 1] == pbase[p]) return;
   uint64_t* rows = (sel[p] ? b1 : b0) + (uint64_t)p * cmax * sw;
   const int64_t n = cnt[p] < cmax ? cnt[p] : cmax;
-  for (int64_t r = threadIdx.x; r < n; r += 256) off_resolve_row(rows + r * sw, q, -1);
+  for (int64_t r = threadIdx.x; r < n; r += 256) off_resolve_row<LISTS>(rows + r * sw, q, -1);
 }
 
 // Rows [r0, r1) of a flat row array (the closed store's rows appended by this push).
+template <bool LISTS>
 __global__ __launch_bounds__(256) void k_off_resolve_rows(uint64_t* __restrict__ rows, int64_t r0, int64_t r1, int sw,
                                                           OffResolve q) {
   for (int64_t r = r0 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < r1; r += (int64_t)gridDim.x * blockDim.x)
-    off_resolve_row(rows + r * sw, q, -1);
+    off_resolve_row<LISTS>(rows + r * sw, q, -1);
 }
 
 // Global-atomic engine, after k_finalize: one thread per accepted record finds the resident slots
 // of its (key, window)s again and stores where the slot's sequence word is its own.  Work scales
 // with the push (<= fan-out probes per record), not with the table.
+template <bool LISTS>
 __global__ __launch_bounds__(256) void k_off_resolve_probe(ApplyParams p, const int64_t* __restrict__ hkeys,
                                                            const int64_t* __restrict__ keys,
                                                            const int64_t* __restrict__ ts,
@@ -492,7 +505,7 @@ __global__ __launch_bounds__(256) void k_off_resolve_probe(ApplyParams p, const 
       const int64_t w1 = (int64_t)s[1];
       if (w1 == EMPTY_WS) break;  // (a late window of this record may have no group)
       if (w1 == ws && (int64_t)s[0] == key) {
-        off_resolve_row(s, q, seq);
+        off_resolve_row<LISTS>(s, q, seq);
         break;
       }
       slot = (slot + 1) & mask;
@@ -1163,6 +1176,11 @@ static inline bool agg_is_topk(int32_t kind) {
   const int b = agg_base_kind(kind);
   return b == KHIP_AGG_TOPK || b == KHIP_AGG_TOPKDISTINCT;
 }
+static inline bool off_has_lists(const OffResolve& q) {
+  for (int k = 0; k < q.n; k++)
+    if (q.a[k].n) return true;
+  return false;
+}
 static inline bool agg_is_offset(int32_t kind) {
   const int b = agg_base_kind(kind);
   return b == KHIP_AGG_LATEST_BY_OFFSET || b == KHIP_AGG_EARLIEST_BY_OFFSET;
@@ -1173,7 +1191,8 @@ static khip_status plan_state(khip_agg* a) {
   int word = 3;  // w0, w1, rowtime
   int w_star = -1;
   // offset aggregates: the hidden sequence columns (one per argument column of an ignore-nulls
-  // form, whose validity it takes, and one without validity for the KEEP_NULLS forms), and first
+  // form, whose validity it takes, and one without validity for the KEEP_NULLS forms; EARLIEST's
+  // N forms have complemented twins of these), and first
   // in the row the value / null words no update op writes (the sequence words come last: the
   // engines keep every word up to the highest op word)
   a->n_hidden = 0;
@@ -1184,22 +1203,34 @@ static khip_status plan_state(khip_agg* a) {
     const khip_agg_spec& s = a->aggs[i];
     if (!agg_is_offset(s.kind)) continue;
     const int src = (s.kind & KHIP_AGG_KEEP_NULLS) ? -1 : s.arg_col;
+    // the N forms (agg_k[i] = N >= 1): N value words, one null-mask word (KEEP_NULLS), LATEST's
+    // resolve mark; EARLIEST reads the complemented sequence column (OffSpec)
+    const int N = a->agg_k[i];
+    const bool latest = agg_base_kind(s.kind) == KHIP_AGG_LATEST_BY_OFFSET;
+    const bool neg = N > 0 && !latest;
+    if (N > 29 || a->offs.n >= MAX_OFFS) return fail(KHIP_E_UNSUPPORTED, "too many aggregate state words (max 29)");
     int h = -1;
     for (int k = 0; k < a->n_hidden; k++)
-      if (a->hid_src[k] == src) h = k;
+      if (a->hid_src[k] == src && a->hid_not[k] == neg) h = k;
     if (h < 0) {
       if (d.n_cols + a->n_hidden >= MAX_COLS)
         return fail(KHIP_E_UNSUPPORTED, "offset aggregates: value columns + hidden sequence columns above 8");
       h = a->n_hidden++;
       a->hid_src[h] = src;
+      a->hid_not[h] = neg;
     }
     off_hid[i] = d.n_cols + h;
     OffSpec o{};
     o.col = (int8_t)s.arg_col;
     o.type = (int8_t)a->col_types[s.arg_col];
-    o.w_val = (int16_t)word++;
+    o.n = (int8_t)N;
+    o.earliest = neg ? 1 : 0;
+    o.w_val = (int16_t)word;
+    word += std::max(N, 1);
     o.w_null = (s.kind & KHIP_AGG_KEEP_NULLS) ? (int16_t)word++ : (int16_t)-1;
+    o.w_mark = (N > 0 && latest) ? (int16_t)word++ : (int16_t)-1;
     o.w_seq = -1;
+    if (word > 32) return fail(KHIP_E_UNSUPPORTED, "too many aggregate state words (max 29)");
     a->out_off[i] = a->offs.n;
     a->offs.a[a->offs.n++] = o;
   }
@@ -1226,6 +1257,7 @@ static khip_status plan_state(khip_agg* a) {
   }
   for (int i = 0; i < d.n_aggs; i++) {  // latest = MAX(seq), earliest = MIN(seq); no non-null count:
     if (off_hid[i] < 0) continue;       // the initial value itself says "no record yet"
+    if (a->agg_k[i] > 0) continue;      // (the N forms: slots, below)
     const int h = off_hid[i];
     const bool latest = agg_base_kind(a->aggs[i].kind) == KHIP_AGG_LATEST_BY_OFFSET;
     int& w = latest ? w_max[h] : w_min[h];
@@ -1242,6 +1274,24 @@ static khip_status plan_state(khip_agg* a) {
   a->has_topk = false;
   for (int i = 0; i < d.n_aggs; i++) {
     const khip_agg_spec& s = a->aggs[i];
+    if (off_hid[i] >= 0 && a->agg_k[i] > 0) {
+      // the N forms of the offset aggregates: "the last / first N records" = the N largest keys of
+      // the hidden (complemented) sequence column, a TOPK span per (hidden column, N).  A key is
+      // never INT64_MIN (seq >= 0, ~seq > INT64_MIN): the list's length is the leading non-empty
+      // slots, no count word
+      a->has_topk = true;
+      const int k = a->agg_k[i];
+      for (size_t j = 0; j < spans.size(); j++)
+        if (spans[j].kind == KHIP_AGG_TOPK && spans[j].col == off_hid[i] && spans[j].k == k) out_span[i] = (int)j;
+      if (out_span[i] < 0) {
+        if (word + k > 32) return fail(KHIP_E_UNSUPPORTED, "too many aggregate state words (max 29)");
+        out_span[i] = (int)spans.size();
+        spans.push_back(TopkSpan{KHIP_AGG_TOPK, off_hid[i], k, word});
+        word += k;
+      }
+      a->offs.a[a->out_off[i]].w_seq = (int16_t)spans[out_span[i]].word;
+      continue;
+    }
     if (!agg_is_topk(s.kind)) continue;
     a->has_topk = true;
     const int k = a->agg_k[i];
@@ -1460,7 +1510,8 @@ khip_status khip_agg_result_type(const khip_agg_desc* d, int32_t i, int32_t* out
 khip_status khip_agg_result_len(const khip_agg_desc* d, int32_t i, int32_t* out) {
   if (!d || !out || i < 0 || i >= d->n_aggs) return fail(KHIP_E_INVALID, "bad aggregate index");
   const khip_agg_spec& s = d->aggs[i];
-  *out = agg_is_topk(s.kind) ? std::max(agg_k_bits(s.kind), 1) : 1;
+  // (the N forms of LATEST / EARLIEST_BY_OFFSET: N; their scalar forms carry no k bits)
+  *out = (agg_is_topk(s.kind) || agg_is_offset(s.kind)) ? std::max(agg_k_bits(s.kind), 1) : 1;
   return KHIP_OK;
 }
 
@@ -1488,9 +1539,13 @@ khip_status khip_agg_create(const khip_agg_desc* desc, khip_agg** out) {
     if (bk < KHIP_AGG_COUNT_STAR || bk > KHIP_AGG_TOPKDISTINCT) return fail(KHIP_E_INVALID, "aggregate kind");
     if ((s.kind & KHIP_AGG_KEEP_NULLS) && !agg_is_offset(s.kind))
       return fail(KHIP_E_INVALID, "KHIP_AGG_KEEP_NULLS on an aggregate other than LATEST / EARLIEST_BY_OFFSET");
-    if (agg_is_topk(s.kind) ? agg_k_bits(s.kind) < 1 : agg_k_bits(s.kind) != 0)
-      return fail(KHIP_E_INVALID, agg_is_topk(s.kind) ? "TOPK / TOPKDISTINCT: k (KHIP_AGG_K) must be at least 1"
-                                                      : "KHIP_AGG_K on an aggregate other than TOPK / TOPKDISTINCT");
+    if (agg_is_offset(s.kind)) {  // no k bits: the scalar form; N >= 1: the N form (an ARRAY, also for N = 1)
+      if (agg_k_bits(s.kind) < 0)
+        return fail(KHIP_E_INVALID, "LATEST / EARLIEST_BY_OFFSET: N (KHIP_AGG_K) must be at least 1");
+    } else if (agg_is_topk(s.kind) ? agg_k_bits(s.kind) < 1 : agg_k_bits(s.kind) != 0)
+      return fail(KHIP_E_INVALID, agg_is_topk(s.kind)
+                                      ? "TOPK / TOPKDISTINCT: k (KHIP_AGG_K) must be at least 1"
+                                      : "KHIP_AGG_K on an aggregate other than TOPK / TOPKDISTINCT / the offset kinds");
     if (bk != KHIP_AGG_COUNT_STAR && (s.arg_col < 0 || s.arg_col >= d.n_cols))
       return fail(KHIP_E_INVALID, "aggregate argument column");
     has_offset = has_offset || agg_is_offset(s.kind);
@@ -1908,11 +1963,14 @@ static khip_status off_resolve_part(khip_agg* a, const ColPtrs& cols, int64_t ba
   }
   q.base = base;
   q.rows = m;
-  hipLaunchKernelGGL(k_off_resolve_part, dim3((unsigned)s.P), dim3(256), 0, a->stream, s.buf[0].as<uint64_t>(),
+  const bool lists = off_has_lists(a->offs);  // (an N form: the kernels' list code)
+  auto rpart = lists ? k_off_resolve_part<true> : k_off_resolve_part<false>;
+  auto rrows = lists ? k_off_resolve_rows<true> : k_off_resolve_rows<false>;
+  hipLaunchKernelGGL(rpart, dim3((unsigned)s.P), dim3(256), 0, a->stream, s.buf[0].as<uint64_t>(),
                      s.buf[1].as<uint64_t>(), s.sel.as<uint8_t>(), s.cnt.as<int64_t>(), s.cmax, a->sw,
                      s.pbase.as<int64_t>(), s.last_c1 ? s.prn.as<uint32_t>() : (const uint32_t*)nullptr, q);
   if (s.closed_n > closed0)
-    hipLaunchKernelGGL(k_off_resolve_rows, dim3(grid_for(s.closed_n - closed0, 256, 4096)), dim3(256), 0, a->stream,
+    hipLaunchKernelGGL(rrows, dim3(grid_for(s.closed_n - closed0, 256, 4096)), dim3(256), 0, a->stream,
                        s.closed.as<uint64_t>(), closed0, s.closed_n, a->sw, q);
   KHIP_TRY_HIP(hipGetLastError());
   // the caller's columns (and a host batch's staging copies) are only valid until the push returns
@@ -1974,8 +2032,16 @@ khip_status khip_agg_push(khip_agg* a, const khip_batch* b, khip_batch_stats* st
     hipLaunchKernelGGL(k_off_iota, dim3(grid_for(n, 256, 4096)), dim3(256), 0, a->stream, a->seqbuf.as<int64_t>(), n,
                        a->seq_base);
     KHIP_TRY_HIP(hipGetLastError());
+    bool any_not = false;
+    for (int h = 0; h < a->n_hidden; h++) any_not = any_not || a->hid_not[h];
+    if (any_not) {  // EARLIEST's N forms: the complemented sequence
+      KHIP_TRY(a->nseqbuf.ensure((size_t)n * 8));
+      hipLaunchKernelGGL(k_off_iota_not, dim3(grid_for(n, 256, 4096)), dim3(256), 0, a->stream,
+                         a->nseqbuf.as<int64_t>(), n, a->seq_base);
+      KHIP_TRY_HIP(hipGetLastError());
+    }
     for (int h = 0; h < a->n_hidden; h++) {
-      cols.data[a->desc.n_cols + h] = a->seqbuf.p;
+      cols.data[a->desc.n_cols + h] = a->hid_not[h] ? a->nseqbuf.p : a->seqbuf.p;
       cols.valid[a->desc.n_cols + h] = a->hid_src[h] >= 0 ? cols.valid[a->hid_src[h]] : nullptr;
     }
   }
@@ -2131,7 +2197,8 @@ khip_status khip_agg_push(khip_agg* a, const khip_batch* b, khip_batch_stats* st
     }
     q.base = a->seq_base;
     q.rows = n;
-    hipLaunchKernelGGL(k_off_resolve_probe, dim3(grid_for(n, 256)), dim3(256), 0, a->stream, a->ap, hkeys, keys, ts,
+    auto probe = off_has_lists(q) ? k_off_resolve_probe<true> : k_off_resolve_probe<false>;
+    hipLaunchKernelGGL(probe, dim3(grid_for(n, 256)), dim3(256), 0, a->stream, a->ap, hkeys, keys, ts,
                        kv, rv, n, a->table.as<uint64_t>(), (uint64_t)(a->cap - 1), q);
     KHIP_TRY_HIP(hipGetLastError());
     KHIP_TRY_HIP(hipStreamSynchronize(a->stream));  // (a host batch's staging buffers are reused by the next push)
@@ -2471,6 +2538,29 @@ static khip_status emit_snapshot(khip_agg* a, const std::vector<uint64_t>& rows,
         }
         continue;
       }
+      if (a->out_off[i] >= 0 && a->offs.a[a->out_off[i]].n) {
+        // the N forms of LATEST / EARLIEST_BY_OFFSET: the same layout, oldest first.  len = the
+        // leading non-empty slots; EARLIEST's slots are already oldest first, LATEST's newest first
+        // (element e is value word len - 1 - e).  The values are the argument's bits; null byte 2 =
+        // a NULL element (KEEP_NULLS), 1 = past the end.
+        const OffSpec& f = a->offs.a[a->out_off[i]];
+        const int L = f.n;
+        int len = 0;
+        while (len < L && (int64_t)s[f.w_seq + len] != INT64_MIN) len++;
+        const uint64_t mask = f.w_null >= 0 ? s[f.w_null] : 0ULL;
+        for (int e = 0; e < L; e++) {
+          const int j = f.earliest ? e : len - 1 - e;
+          const bool has = e < len, nul = has && ((mask >> j) & 1ULL);
+          const uint64_t bits = has && !nul ? s[f.w_val + j] : 0ULL;
+          const int64_t at = r * L + e;
+          if (out->agg_values && out->agg_values[i]) {
+            if (o.type == KHIP_TYPE_INT32) ((int32_t*)out->agg_values[i])[at] = (int32_t)(int64_t)bits;
+            else ((uint64_t*)out->agg_values[i])[at] = bits;  // INT64, or DOUBLE bits (NaN payloads, -0.0)
+          }
+          if (out->agg_null && out->agg_null[i]) out->agg_null[i][at] = !has ? 1 : (nul ? 2 : 0);
+        }
+        continue;
+      }
       int64_t iv = 0;
       double dv = 0.0;
       bool isnull = false;
@@ -2730,7 +2820,8 @@ khip_status khip_agg_destroy(khip_agg* a) {
   DevBuf* bufs[] = {&a->table, &a->blockmax, &a->blockprefix, &a->partials, &a->resume, &a->counters,
                     &a->stream_time, &a->st_keys, &a->st_ts, &a->st_kv, &a->st_rv, &a->st_koff,
                     &a->st_kbytes, &a->kid, &a->khash, &a->chg, &a->lostbuf, &a->lostctr,
-                    &a->pst, &a->pst2, &a->st_col, &a->st_agg, &a->st_seen, &a->st_part, &a->seqbuf};
+                    &a->pst, &a->pst2, &a->st_col, &a->st_agg, &a->st_seen, &a->st_part, &a->seqbuf,
+                    &a->nseqbuf};
   for (DevBuf* b : bufs) b->release();
   for (int c = 0; c < MAX_COLS; c++) {
     a->st_cols[c].release();

@@ -73,10 +73,21 @@ struct AggOut {
 // word (the argument's bits of the winning row) and, for the KEEP_NULLS forms, a null word (1 =
 // the winning row's argument was NULL; -1: none).  The value and null words are no update op's:
 // the engines carry them with the row, and the resolve kernels write them before a push returns.
+//
+// The N forms (col, N): n = N >= 1.  w_seq is the first of N slot words an OP_TOPK op keeps over
+// the hidden column: the group's N largest keys, descending, INT64_MIN = empty.  LATEST reads the
+// sequence column, so slot 0 is the newest record; EARLIEST (earliest = 1) reads the complemented
+// one (~seq), so slot 0 is the oldest and a full list never changes.  w_val is the first of N value
+// words, value word j belonging to slot j; w_null (KEEP_NULLS) is one mask word, bit j = element j
+// is NULL.  LATEST has one more word, w_mark = 1 + the newest sequence already resolved (0: none):
+// its resolve shifts the value words and must not do so twice (off_resolve_list).
 struct OffSpec {
   int16_t w_seq, w_val, w_null;
   int8_t col;   // the argument (user) column
   int8_t type;  // its type
+  int16_t w_mark;   // N-form LATEST only (-1: none)
+  int8_t n;         // 0: the scalar form
+  int8_t earliest;  // N forms: the slots hold ~seq
 };
 constexpr int MAX_OFFS = 16;
 struct OffResolve {
@@ -355,9 +366,72 @@ __device__ __forceinline__ int64_t load_col_raw(const ColPtrs& c, int32_t type, 
 // thread per record, so two records winning different aggregates of one group write different
 // words).  Plain vector loads and stores: the sequence words were produced by earlier kernels on the
 // stream (the launch boundary is the fence).
+__device__ __forceinline__ int64_t off_gather(const OffResolve& q, const OffSpec& o, uint64_t i) {
+  if (o.type == KHIP_TYPE_INT32) return (int64_t)((const int32_t*)q.data[o.col])[i];
+  return ((const int64_t*)q.data[o.col])[i];  // INT64, or DOUBLE bits
+}
+
+// One N-form aggregate of row s (OffSpec).  The slots already hold the list's sequence keys; the
+// value words and the null mask follow them here.  m = the slots this push (slice) filled.
+//   EARLIEST: the m new records are the list's tail and old elements keep their places, so only the
+//   in-push slots are gathered: visiting a row again stores the same words.
+//   LATEST: the m new records are slots [0, m), so the old value words and mask bits move up by m
+//   (from the top down: no word is overwritten before it is read; what passes N is the oldest and
+//   falls out), then [0, m) are gathered.  m counts the slots at or above w_mark, which then
+//   becomes slot 0's sequence + 1: a second visit finds m = 0 and returns.
+// `only` >= 0 (the global-atomic engine: one thread per record): the whole aggregate is done by the
+// record whose sequence is the largest in-push sequence in the slots.  It is unique, exists exactly
+// when m > 0, and the words written are this aggregate's alone.
+__device__ __forceinline__ void off_resolve_list(uint64_t* s, const OffResolve& q, const OffSpec& o, int64_t only) {
+  const int N = o.n;
+  uint64_t* slot = s + o.w_seq;
+  uint64_t* val = s + o.w_val;
+  if (o.earliest) {
+    int64_t top = -1;
+    for (int j = 0; j < N; j++) {
+      const int64_t key = (int64_t)slot[j];
+      if (key == INT64_MIN) break;
+      if ((uint64_t)(~key) - (uint64_t)q.base < (uint64_t)q.rows) top = ~key;  // (ascending sequences)
+    }
+    if (top < 0 || (only >= 0 && only != top)) return;
+    uint64_t mask = o.w_null >= 0 ? s[o.w_null] : 0ULL;
+    for (int j = 0; j < N; j++) {
+      const int64_t key = (int64_t)slot[j];
+      if (key == INT64_MIN) break;
+      const uint64_t i = (uint64_t)(~key) - (uint64_t)q.base;
+      if (i >= (uint64_t)q.rows) continue;
+      val[j] = (uint64_t)off_gather(q, o, i);
+      if (o.w_null >= 0) mask = bit_get(q.valid[o.col], (int64_t)i) ? mask & ~(1ULL << j) : mask | (1ULL << j);
+    }
+    if (o.w_null >= 0) s[o.w_null] = mask;
+    return;
+  }
+  const int64_t mark = (int64_t)s[o.w_mark];
+  const int64_t top = (int64_t)slot[0];
+  if (top < mark || (only >= 0 && only != top)) return;  // (an empty slot is below every mark)
+  int m = 1;
+  while (m < N && (int64_t)slot[m] >= mark) m++;
+  for (int j = N - 1; j >= m; j--) val[j] = val[j - m];
+  uint64_t mask = o.w_null >= 0 ? (s[o.w_null] << m) & ((1ULL << N) - 1) : 0ULL;
+  for (int j = 0; j < m; j++) {
+    const uint64_t i = (uint64_t)slot[j] - (uint64_t)q.base;
+    if (i >= (uint64_t)q.rows) continue;  // (every slice is resolved before the next: not reached)
+    val[j] = (uint64_t)off_gather(q, o, i);
+    if (o.w_null >= 0 && !bit_get(q.valid[o.col], (int64_t)i)) mask |= 1ULL << j;
+  }
+  if (o.w_null >= 0) s[o.w_null] = mask;
+  s[o.w_mark] = (uint64_t)(top + 1);
+}
+
+// LISTS: the handle has an N form (a handle with scalar forms only runs the code it always ran).
+template <bool LISTS>
 __device__ __forceinline__ void off_resolve_row(uint64_t* s, const OffResolve& q, int64_t only) {
   for (int k = 0; k < q.n; k++) {
     const OffSpec o = q.a[k];
+    if (LISTS && o.n) {
+      off_resolve_list(s, q, o, only);
+      continue;
+    }
     const int64_t seq = (int64_t)s[o.w_seq];
     const uint64_t i = (uint64_t)seq - (uint64_t)q.base;  // (the "none yet" values land far outside)
     if (i >= (uint64_t)q.rows || (only >= 0 && seq != only)) continue;
@@ -643,11 +717,16 @@ struct khip_agg {
   std::vector<int> out_off;
   int n_hidden = 0;
   int hid_src[MAX_COLS] = {};
-  DevBuf seqbuf;
+  // hid_not[h]: the column holds ~seq (nseqbuf): EARLIEST's N forms, whose N largest keys are the
+  // N smallest sequences
+  bool hid_not[MAX_COLS] = {};
+  DevBuf seqbuf, nseqbuf;
   int64_t seq_base = 0;  // rows pushed since the handle's creation or last reset
   // ---- TOPK / TOPKDISTINCT: aggs[i].kind holds the bare kind (the caller's KHIP_AGG_K bits are
   // agg_k[i], 0 for a scalar aggregate); out_flag[i]: the TOPKDISTINCT(BIGINT) flag word, or -1.
-  // has_topk: only k_part_agg / k_apply run this handle's records (part_push: merge_allow).
+  // The N forms of the offset aggregates keep their N in agg_k[i] too (0: the scalar form).
+  // has_topk: only k_part_agg / k_apply run this handle's records (part_push: merge_allow); set by
+  // the N forms as well, whose slots are OP_TOPK ops.
   std::vector<int> agg_k, out_flag;
   bool has_topk = false;
   int sw = 4;

@@ -834,6 +834,20 @@ khip_status khip_serde_destroy(khip_serde* s);
 #define KHIP_SINK_SRC_WS (-2)   /* value column source: WINDOWSTART                            */
 #define KHIP_SINK_SRC_WE (-3)   /* value column source: WINDOWEND                              */
 
+/* ARRAY value columns (the results of TOPK / TOPKDISTINCT and of the N forms of LATEST / EARLIEST_
+ * BY_OFFSET), OR-ed into a khip_sink_desc.value_types entry like KHIP_AGG_K into a kind: no such
+ * bits is a scalar column; KHIP_SINK_ARRAY(L), 1 <= L <= 32767, an ARRAY of the base type (INT32 /
+ * INT64 / DOUBLE) with L slots per row, L being khip_agg_result_len() of the aggregate behind the
+ * column (the sink has no 29-word limit of its own).  Only a JSON value carries one (the reference
+ * rejects such a statement for DELIMITED and KAFKA at plan time): the column prints, after its
+ * name, as the compact list [e0,e1,...], every element as a scalar of its type prints (a NULL
+ * element as null, a non-finite DOUBLE as its string), the empty list as []; the column itself is
+ * never SQL NULL.  The row's list: see khip_sink_rows.  KHIP_E_INVALID from khip_sink_create: an
+ * ARRAY column with value format KAFKA or DELIMITED; the bits on a KHIP_SINK_SRC_WS / _WE column;
+ * negative bits; two value columns reading one rows column with different L or base type when
+ * either is an ARRAY.  Key columns are scalar: the bits on a key type are an unknown key type. */
+#define KHIP_SINK_ARRAY(L) ((int32_t)(L) << 16)
+
 typedef struct khip_sink_desc {
   int32_t key_format;              /* KHIP_FMT_KAFKA / JSON / DELIMITED                          */
   int32_t n_key_cols;              /* 1..KHIP_SINK_MAX_COLS (KAFKA: 1)                            */
@@ -842,7 +856,7 @@ typedef struct khip_sink_desc {
   int32_t window_kind;             /* KHIP_WINDOW_*: the table's window (NONE: plain key)        */
   int32_t value_format;            /* KHIP_FMT_KAFKA / JSON / DELIMITED                          */
   int32_t n_value_cols;            /* 0..KHIP_SINK_MAX_COLS (KAFKA: 1)                            */
-  const int32_t* value_types;      /* KHIP_TYPE_INT32 / INT64 / DOUBLE                            */
+  const int32_t* value_types;      /* KHIP_TYPE_INT32 / INT64 / DOUBLE [| KHIP_SINK_ARRAY(L)]     */
   const char* const* value_names;  /* JSON field names, in output column order                   */
   const int32_t* value_src;        /* rows column index, or KHIP_SINK_SRC_WS / KHIP_SINK_SRC_WE   */
   int32_t delimiter;               /* DELIMITED: the delimiter byte (0 = ',')                     */
@@ -869,7 +883,12 @@ typedef struct khip_key_col {
  * input's. */
 khip_status khip_sink_key(khip_sink* s, const khip_batch* in, const khip_key_col* cols, khip_batch* out);
 
-/* Rows in khip_snapshot layout (what khip_agg_changes / khip_agg_snapshot write). */
+/* Rows in khip_snapshot layout (what khip_agg_changes / khip_agg_snapshot write).
+ * A rows column src that a KHIP_SINK_ARRAY(L) value column reads holds n_rows x L elements in
+ * col_data[src] and n_rows x L bytes in col_null[src], row-major.  A row's list is its leading
+ * slots up to the first byte that is neither 0 nor 2: byte 0 is an element, byte 2 a NULL element
+ * (printed null), byte 1 is past the end.  The list's length lives only in these bytes, so
+ * khip_sink_encode answers KHIP_E_INVALID when col_null[src] of such a column is NULL. */
 typedef struct khip_sink_rows {
   int64_t n_rows;
   int32_t mem;                     /* KHIP_MEM_HOST or KHIP_MEM_DEVICE (every pointer below)     */
@@ -880,7 +899,8 @@ typedef struct khip_sink_rows {
   const int64_t* window_start;
   const int64_t* window_end;
   const void* const* col_data;     /* the value sources (agg results); element type from desc     */
-  const uint8_t* const* col_null;  /* 1 byte per row, 1 = NULL (entries may be NULL)             */
+  const uint8_t* const* col_null;  /* 1 byte per row, 1 = NULL (entries may be NULL); an ARRAY
+                                      column: 1 byte per slot, required (see above)              */
   const uint8_t* tombstone;        /* 1 byte per row, 1 = delete → null value (may be NULL)      */
 } khip_sink_rows;
 

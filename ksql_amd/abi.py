@@ -185,6 +185,17 @@ class SinkOut(C.Structure):
 
 FMT = {"NONE": 0, "KAFKA": 1, "DELIMITED": 2, "JSON": 3, "AVRO": 4}
 SINK_SRC = {"WS": -2, "WE": -3}
+
+
+def SINK_ARRAY(L):
+    """KHIP_SINK_ARRAY(L): an ARRAY value column of L slots per row, OR-ed into its element type."""
+    return int(L) << 16
+
+
+# khip_sink.hip's SK_ABUF: the value bytes of a 256-row tile that a sink with an ARRAY column stages
+# per round (tests build tiles on both sides of it)
+SINK_ARRAY_STAGE = 32768
+
 AVRO_TYPE = {"boolean": 1, "int": 2, "long": 3, "float": 4, "double": 5, "string": 6, "bytes": 7}
 TYPE_STRING = 3
 COMM_ID_BYTES = 128
@@ -1094,15 +1105,21 @@ class SinkHandle:
     def __init__(self, lib, key_format, key_cols, value_format, value_cols, window_kind="NONE", delimiter=",",
                  device=0):
         """key_cols: [(name, type)]; value_cols: [(name, type, src)] with src a rows column index or
-        "WS" / "WE"; types INT32 / INT64 / DOUBLE / STRING (keys)."""
+        "WS" / "WE"; types INT32 / INT64 / DOUBLE / STRING (keys).  (name, type, src, L) is an ARRAY
+        column of L slots per row (KHIP_SINK_ARRAY(L); JSON values), type its element type."""
         self.lib = lib
         tmap = dict(TYPE, STRING=TYPE_STRING)
         nk, nv = len(key_cols), len(value_cols)
-        self._kt = (i32 * max(nk, 1))(*[tmap[t] for _, t in key_cols])
+        # rows column -> L of the ARRAY columns (encode() takes their (n, L) values and null bytes)
+        self.array_len = {c[2]: c[3] for c in value_cols if len(c) > 3 and not isinstance(c[2], str)}
+
+        def code(t):  # a type name, or the ABI's integer as it is
+            return t if isinstance(t, int) else tmap[t]
+        self._kt = (i32 * max(nk, 1))(*[code(t) for _, t in key_cols])
         self._kn = (C.c_char_p * max(nk, 1))(*[n.encode() for n, _ in key_cols])
-        self._vt = (i32 * max(nv, 1))(*[tmap[t] for _, t, _ in value_cols])
-        self._vn = (C.c_char_p * max(nv, 1))(*[n.encode() for n, _, _ in value_cols])
-        self._vs = (i32 * max(nv, 1))(*[SINK_SRC[s] if isinstance(s, str) else s for _, _, s in value_cols])
+        self._vt = (i32 * max(nv, 1))(*[code(c[1]) | (SINK_ARRAY(c[3]) if len(c) > 3 else 0) for c in value_cols])
+        self._vn = (C.c_char_p * max(nv, 1))(*[c[0].encode() for c in value_cols])
+        self._vs = (i32 * max(nv, 1))(*[SINK_SRC[c[2]] if isinstance(c[2], str) else c[2] for c in value_cols])
         self.key_cols, self.value_cols = key_cols, value_cols
         self.desc = SinkDesc(FMT[key_format], nk, self._kt, self._kn, WINDOW[window_kind], FMT[value_format], nv,
                              self._vt, self._vn, self._vs, ord(delimiter), device)
@@ -1162,20 +1179,29 @@ class SinkHandle:
                               bitorder="little")[:n].astype(bool)
         return [data[offs[i]:offs[i + 1]] if valid[i] else None for i in range(n)]
 
-    def encode(self, snap, tombstone=None, key_serialized=False, device_out=False, align=0):
+    def encode(self, snap, tombstone=None, key_serialized=False, device_out=False, align=0, device_rows=False):
         """snap: a snapshot dict (AggHandle.snapshot() / changes() layout: key or key_bytes/key_offsets,
         ws, we, values, nulls); host rows.  Returns (keys, values): lists of bytes / None.
-        device_out: into device buffers (the one-pass encoder), `align` bytes past 16-byte alignment."""
+        device_out: into device buffers (the one-pass encoder), `align` bytes past 16-byte alignment.
+        device_rows: the rows are copied to the device with torch and passed as KHIP_MEM_DEVICE rows.
+        An ARRAY column j takes values[j] of shape (n, L) and the library's null bytes: the dict's
+        null_bytes[j], or for rows built by hand a uint8 (n, L) array under nulls[j] (the boolean
+        nulls[j] of a snapshot cannot tell a NULL element from the list's end)."""
         n = int(snap["n"])
         keep = []
 
         def arr(a, dtype):
             a = np.ascontiguousarray(a, dtype)
+            if device_rows:
+                import torch
+                a = torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).cuda()
+                keep.append(a)
+                return a.data_ptr()
             keep.append(a)
             return a.ctypes.data
         rows = SinkRows()
         rows.n_rows = n
-        rows.mem = MEM_HOST
+        rows.mem = MEM_DEVICE if device_rows else MEM_HOST
         rows.key_serialized = 1 if key_serialized else 0
         if snap.get("key_offsets") is None and len(snap.get("key", [])) and isinstance(snap["key"][0], (str, bytes)):
             enc = [k.encode("utf-8", "surrogateescape") if isinstance(k, str) else k for k in snap["key"]]
@@ -1192,10 +1218,18 @@ class SinkHandle:
         nulls = snap.get("nulls", [])
         cd = (C.c_void_p * max(len(vals), 1))()
         cn = (C.c_void_p * max(len(vals), 1))()
+        nbytes = snap.get("null_bytes")
         for j, v in enumerate(vals):
             v = np.asarray(v)
+            nj = nulls[j] if j < len(nulls) else None
+            if j in self.array_len:
+                nj = nbytes[j] if nbytes is not None else nj
+                if nj is not None:
+                    nj = np.asarray(nj)
+                    if v.shape != (n, self.array_len[j]) or nj.shape != v.shape or nj.dtype != np.uint8:
+                        raise ValueError("ARRAY column %d: values and uint8 null bytes of shape (n, L)" % j)
             cd[j] = arr(v, v.dtype)
-            cn[j] = arr(np.asarray(nulls[j], np.uint8), np.uint8) if j < len(nulls) and nulls[j] is not None else None
+            cn[j] = arr(np.asarray(nj, np.uint8), np.uint8) if nj is not None else None
         rows.col_data = cd
         rows.col_null = cn
         if tombstone is not None:

@@ -11,7 +11,9 @@
 // tile's lengths in the block, adds the tile's carry and writes each record at its offset, and
 // the offsets.  A KAFKA INT32 / BIGINT key has a fixed width (no key lengths; a BIGINT key and its
 // window suffix leave as 8-byte words), and a JSON column's '{' / ',' + escaped name + ':' is built
-// once on the host.  Doubles print
+// once on the host.  A sink with an ARRAY value column (KHIP_SINK_ARRAY: JSON lists) runs its own
+// instantiations, k_sink_measure<true> and k_sink_write_arr; a scalar sink's kernels carry none
+// of it.  Doubles print
 // through the Schubfach shortest-decimal algorithm (R. Giulietti 2020; java.lang.Double.toString
 // since JDK 19) with the 126-bit powers of ten of tools/gen_dtoa.py, so every digit is computed
 // exactly with 64-bit integer arithmetic.  Byte parity of DOUBLE text therefore assumes the
@@ -58,6 +60,9 @@ struct SinkParams {
   int32_t kpre_len[SK_MAX], vpre_len[SK_MAX];
   alignas(8) uint8_t kpre[SK_MAX][SK_PRE];
   alignas(8) uint8_t vpre[SK_MAX][SK_PRE];
+  // ARRAY value columns (JSON values only): the slots per row, KHIP_SINK_ARRAY's L; 0 = the scalar
+  // column (vtype is the element type either way)
+  int32_t varr[SK_MAX];
 };
 
 // ------------------------------------------------------------------ writers
@@ -76,6 +81,23 @@ struct HostW {  // host: a JSON column prefix (SinkParams::kpre / vpre)
   void put(uint8_t c) {
     if (n < cap) p[n] = c;
     n++;
+  }
+};
+constexpr int SK_ABUF = 32768;  // k_sink_write_arr's stage: a tile's value bytes per round
+// WinW keeps the bytes that fall into a window of SK_ABUF bytes of LDS; rel: the next byte's place in
+// it, negative while a row that began in the window before is still outside.  b is an LDS
+// address-space pointer, so that the stores are DS instructions.  Through a generic pointer they
+// are FLAT stores, and the hardware picks a FLAT access's aperture from the base register without
+// the instruction's offset field: consecutive puts compile to one base and offsets :1, :2, ..., and
+// with rel < 0 at the first of them and the stage at LDS offset 0 that base lies below the LDS
+// aperture (a memory aperture violation, although every stored byte is inside the window).
+typedef __attribute__((address_space(3))) uint8_t sk_lds_u8;
+struct WinW {
+  sk_lds_u8* b;
+  int64_t rel;
+  __device__ __forceinline__ void put(uint8_t c) {
+    if ((uint64_t)rel < (uint64_t)SK_ABUF) b[rel] = c;
+    rel++;
   }
 };
 struct BufW {  // a field's text, for the CSV quoting decision
@@ -431,8 +453,11 @@ __device__ void put_key(W& w, const SinkParams& q, F&& kval) {
   }
 }
 
-template <class W, class F>
-__device__ __forceinline__ void put_value(W& w, const SinkParams& q, F&& vval) {
+// ARR: the instantiation for sinks with an ARRAY column; velem(c, e, v) fetches element e of the
+// row's list in column c and answers false at the list's end (the one rule of row_elem).  Without
+// ARR velem is never called and the code is the scalar encoder's.
+template <bool ARR, class W, class F, class G>
+__device__ __forceinline__ void put_value(W& w, const SinkParams& q, F&& vval, G&& velem) {
   if (q.value_format == KHIP_FMT_KAFKA) {
     put_kafka_val(w, q.vtype[0], vval(0));
   } else if (q.value_format == KHIP_FMT_JSON) {
@@ -444,6 +469,16 @@ __device__ __forceinline__ void put_value(W& w, const SinkParams& q, F&& vval) {
         w.put(i ? ',' : '{');
         put_json_str(w, q.vname[i], q.vname_len[i]);
         w.put(':');
+      }
+      if (ARR && q.varr[i] > 0) {
+        w.put('[');
+        Val v;
+        for (int e = 0; velem(i, e, v); e++) {
+          if (e) w.put(',');
+          put_json_val(w, q.vtype[i], v);
+        }
+        w.put(']');
+        continue;
       }
       put_json_val(w, q.vtype[i], vval(i));
     }
@@ -494,6 +529,21 @@ __device__ __forceinline__ Val row_value_val(const SinkParams& q, const RowsDev&
     else v.i = ((const int64_t*)r.col[src])[i];  // INT64, DOUBLE bits
   }
   return v;
+}
+
+// Element e of row i's list in ARRAY column c (L slots per row, khip_snapshot's layout): the list is
+// the row's leading slots whose null byte is 0 (an element) or 2 (a NULL element); any other byte,
+// or slot L, ends it.  The measure pass and the write pass both read the length here.
+__device__ __forceinline__ bool row_elem(const SinkParams& q, const RowsDev& r, int64_t i, int c, int e, Val& v) {
+  const int L = q.varr[c], src = q.vsrc[c];
+  if (e >= L) return false;
+  const int64_t at = i * L + e;
+  const uint8_t nb = r.cnull[src][at];
+  if (nb != 0 && nb != 2) return false;
+  v = Val{0, nullptr, 0, nb == 2};
+  if (q.vtype[c] == KHIP_TYPE_INT32) v.i = ((const int32_t*)r.col[src])[at];
+  else v.i = ((const int64_t*)r.col[src])[at];
+  return true;
 }
 
 // The row's window bounds, loaded before any of its bytes are stored.
@@ -591,6 +641,7 @@ __device__ __forceinline__ void sk_block_scan2(int64_t& a, int64_t& b, int64_t& 
 
 // Pass 1: each row's key / value length at klen / vlen[i + 1] (keys skipped when every key is kfix
 // bytes), each tile's sums at tsum[1 + tile] (keys) and tsum[nT + 2 + tile] (values).
+template <bool ARR>
 __global__ __launch_bounds__(256) void k_sink_measure(const SinkParams* __restrict__ qp, RowsDev r, int64_t n, int kfix,
                                                       int64_t nT, int64_t* __restrict__ klen, int64_t* __restrict__ vlen,
                                                       int64_t* __restrict__ tsum) {
@@ -609,7 +660,9 @@ __global__ __launch_bounds__(256) void k_sink_measure(const SinkParams* __restri
       sk += kw.n;
     }
     CountW vw;
-    if (!value_is_null(q, r, i)) put_value(vw, q, [&](int c) { return row_value_val(q, r, i, c); });
+    if (!value_is_null(q, r, i))
+      put_value<ARR>(vw, q, [&](int c) { return row_value_val(q, r, i, c); },
+                     [&](int c, int e, Val& v) { return row_elem(q, r, i, c, e, v); });
     vlen[i + 1] = vw.n;
     sv += vw.n;
   }
@@ -649,12 +702,18 @@ __device__ __forceinline__ void put_key_words(const SinkParams& q, const RowsDev
 // A wave's value bytes, staged contiguously in LDS (lds[0..L)), to dst[0..L): 16-byte aligned
 // chunks, one per lane and round — whole 16-byte stores inside, bytes at the two edge chunks
 // (shared with the neighbouring waves).  lds has 16 readable bytes past L.
+// sk_range_copy<NT>: the same by NT threads, this one being thread t (k_sink_write_arr: the block).
+template <int NT>
+__device__ __forceinline__ void sk_range_copy(const uint8_t* lds, int L, uint8_t* __restrict__ dst, int t);
 __device__ __forceinline__ void sk_wave_copy(const uint8_t* lds, int L, uint8_t* __restrict__ dst) {
-  const int lane = threadIdx.x & 63;
+  sk_range_copy<64>(lds, L, dst, threadIdx.x & 63);
+}
+template <int NT>
+__device__ __forceinline__ void sk_range_copy(const uint8_t* lds, int L, uint8_t* __restrict__ dst, int t) {
   const int A = (int)((uintptr_t)dst & 15);
   const int nch = (A + L + 15) >> 4;
   const uint32_t* l32 = (const uint32_t*)lds;
-  for (int c = lane; c < nch; c += 64) {
+  for (int c = t; c < nch; c += NT) {
     const int o = 16 * c - A;
     uint8_t* g = dst + o;
     if (o >= 0 && o + 16 <= L) {
@@ -725,9 +784,10 @@ __global__ KHIP_SINK_WRITE_LB void k_sink_write(const SinkParams* __restrict__ q
   auto vget = [&](int c) {
     return c == 0 ? v0 : c == 1 ? v1 : c == 2 ? v2 : c == 3 ? v3 : row_value_val(q, r, i, c);
   };
+  auto no_elem = [](int, int, Val&) { return false; };  // (a scalar sink has no ARRAY column)
   if (in && staged && !isnull) {
     MemW vw{vls + (vo - wbase)};
-    put_value(vw, q, vget);
+    put_value<false>(vw, q, vget, no_elem);
   }
   __syncthreads();
   if (staged && wlen > 0) sk_wave_copy(vls, (int)wlen, vb + wbase);
@@ -741,10 +801,73 @@ __global__ KHIP_SINK_WRITE_LB void k_sink_write(const SinkParams* __restrict__ q
     sk_st(vnull + i, (uint8_t)(isnull ? 1 : 0));
     if (!staged && !isnull) {
       MemW vw{vb + vo};
-      put_value(vw, q, vget);
+      put_value<false>(vw, q, vget, no_elem);
     }
     sk_st(koff + i + 1, ko + kl);
     sk_st(voff + i + 1, vo + vl);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    koff[0] = 0;
+    voff[0] = 0;
+  }
+}
+
+// Pass 2 of a sink with an ARRAY column (a JSON value): k_sink_write's offsets, keys and outputs,
+// with another way for the values out.  A row with lists is long (64 rows pass SK_WBUF at 32 bytes
+// each), so the stage is the tile's: the tile's values are one contiguous range of tv bytes, and
+// the block goes over it in rounds of SK_ABUF bytes.  In a round every row that overlaps the
+// round's window encodes itself through WinW, which keeps the bytes inside the window (a row across
+// a window's edge encodes twice, each window taking its part), and the 256 threads copy the window
+// out in 16-byte stores.  A round's element loads come while only LDS is written; the next round's
+// wait once for the round's stores.  Rounds are uniform over the block (tv is), so the barriers
+// are too.  32 KB of LDS: four blocks per CU, the four waves per SIMD the register cap gives.
+__global__ KHIP_SINK_WRITE_LB void k_sink_write_arr(const SinkParams* __restrict__ qp, RowsDev r, int64_t n, int kfix,
+                                                    int kwords, int64_t nT, const int64_t* __restrict__ tsum,
+                                                    int64_t* __restrict__ koff, uint8_t* __restrict__ kb,
+                                                    int64_t* __restrict__ voff, uint8_t* __restrict__ vb,
+                                                    uint8_t* __restrict__ vnull) {
+  __shared__ int64_t ws[2][4];
+  __shared__ uint32_t ast[SK_ABUF / 4 + 4];
+  const SinkParams& q = *qp;
+  const int64_t i = (int64_t)blockIdx.x * SK_TILE + threadIdx.x;
+  const bool in = i < n;
+  const int64_t kl = !in ? 0 : kfix ? kfix : koff[i + 1];
+  const int64_t vl = in ? voff[i + 1] : 0;
+  int64_t ko = kl, vo = vl, tk, tv;
+  sk_block_scan2(ko, vo, tk, tv, ws);
+  ko += kfix ? (int64_t)blockIdx.x * SK_TILE * kfix : tsum[blockIdx.x];
+  const int64_t tbase = tsum[nT + 1 + blockIdx.x];  // the tile's first value byte; vo: the row's, within the tile
+  const bool isnull = in ? value_is_null(q, r, i) : true;
+  Val v0{0, nullptr, 0, true}, v1 = v0, v2 = v0, v3 = v0;  // the first four value columns (scalars)
+  if (!isnull) {
+    if (q.n_val > 0 && !q.varr[0]) v0 = row_value_val(q, r, i, 0);
+    if (q.n_val > 1 && !q.varr[1]) v1 = row_value_val(q, r, i, 1);
+    if (q.n_val > 2 && !q.varr[2]) v2 = row_value_val(q, r, i, 2);
+    if (q.n_val > 3 && !q.varr[3]) v3 = row_value_val(q, r, i, 3);
+  }
+  auto vget = [&](int c) {
+    return c == 0 ? v0 : c == 1 ? v1 : c == 2 ? v2 : c == 3 ? v3 : row_value_val(q, r, i, c);
+  };
+  const uint8_t* als = (const uint8_t*)ast;
+  for (int64_t lo = 0; lo < tv; lo += SK_ABUF) {
+    if (!isnull && vo < lo + SK_ABUF && vo + vl > lo) {
+      WinW vw{(sk_lds_u8*)ast, vo - lo};
+      put_value<true>(vw, q, vget, [&](int c, int e, Val& v) { return row_elem(q, r, i, c, e, v); });
+    }
+    __syncthreads();
+    sk_range_copy<256>(als, (int)(tv - lo < SK_ABUF ? tv - lo : SK_ABUF), vb + tbase + lo, threadIdx.x);
+    __syncthreads();
+  }
+  if (in) {
+    if (kwords) {
+      put_key_words(q, r, i, (uint64_t*)(kb + ko));
+    } else {
+      MemW kw{kb + ko};
+      encode_key_row(kw, q, r, i);
+    }
+    sk_st(vnull + i, (uint8_t)(isnull ? 1 : 0));
+    sk_st(koff + i + 1, ko + kl);
+    sk_st(voff + i + 1, tbase + vo + vl);
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     koff[0] = 0;
@@ -881,6 +1004,8 @@ struct khip_sink {
   khip_sink_desc desc{};
   SinkParams q{};
   int device = 0;
+  bool has_arr = false;        // some value column is an ARRAY: the k_sink_*<true> / _arr kernels
+  int32_t src_len[SK_MAX] = {};  // per rows column: its ARRAY length L, 0 = scalar
   hipStream_t stream = nullptr;
   DevBuf dq, bsum, bsum2, tsum, koff, kbytes, kvalid, voff, vbytes, vnull;
   DevBuf st_key, st_koff, st_kbytes, st_ws, st_we, st_tomb, st_col[SK_MAX], st_null[SK_MAX], st_cv[SK_MAX];
@@ -969,9 +1094,24 @@ khip_status khip_sink_create(const khip_sink_desc* d, khip_sink** out) {
       return fail(KHIP_E_INVALID, "JSON key column names (<= 64 bytes) required");
     }
   }
+  int src_type[SK_MAX];
+  for (int c = 0; c < SK_MAX; c++) src_type[c] = -1;
   for (int i = 0; i < q.n_val; i++) {
-    q.vtype[i] = d->value_types[i];
+    if (d->value_types[i] < 0) {
+      delete s;
+      return fail(KHIP_E_INVALID, "value column type: negative KHIP_SINK_ARRAY bits");
+    }
+    q.vtype[i] = d->value_types[i] & 0xFFFF;
+    q.varr[i] = d->value_types[i] >> 16;  // KHIP_SINK_ARRAY(L): 1..32767, 0 = scalar
     q.vsrc[i] = d->value_src[i];
+    if (q.varr[i] && vf != KHIP_FMT_JSON) {
+      delete s;
+      return fail(KHIP_E_INVALID, "an ARRAY value column needs the JSON value format (KAFKA / DELIMITED carry no arrays)");
+    }
+    if (q.varr[i] && (q.vsrc[i] == KHIP_SINK_SRC_WS || q.vsrc[i] == KHIP_SINK_SRC_WE)) {
+      delete s;
+      return fail(KHIP_E_INVALID, "WINDOWSTART / WINDOWEND are scalar BIGINT columns, not ARRAYs");
+    }
     if (!sk_type_ok(q.vtype[i], false) || q.vsrc[i] < KHIP_SINK_SRC_WE || q.vsrc[i] >= SK_MAX ||
         q.vsrc[i] == -1) {
       delete s;
@@ -980,6 +1120,16 @@ khip_status khip_sink_create(const khip_sink_desc* d, khip_sink** out) {
     if (q.vsrc[i] < 0 && q.vtype[i] != KHIP_TYPE_INT64) {
       delete s;
       return fail(KHIP_E_INVALID, "WINDOWSTART / WINDOWEND are BIGINT");
+    }
+    if (q.vsrc[i] >= 0) {  // two readers of one rows column agree on its layout when one is an ARRAY
+      const int c = q.vsrc[i];
+      if (src_type[c] >= 0 && (s->src_len[c] || q.varr[i]) && (s->src_len[c] != q.varr[i] || src_type[c] != q.vtype[i])) {
+        delete s;
+        return fail(KHIP_E_INVALID, "value columns read rows column " + std::to_string(c) + " with different ARRAY lengths or types");
+      }
+      src_type[c] = q.vtype[i];
+      s->src_len[c] = q.varr[i];
+      s->has_arr |= q.varr[i] > 0;
     }
     if (vf == KHIP_FMT_JSON && !name(d->value_names, i, q.vname[i], &q.vname_len[i])) {
       delete s;
@@ -1115,6 +1265,8 @@ khip_status khip_sink_encode(khip_sink* s, const khip_sink_rows* rows, khip_sink
     if (src == KHIP_SINK_SRC_WE && n && !rows->window_end) return fail(KHIP_E_INVALID, "WINDOWEND source");
     if (src >= 0) {
       if (n && (!rows->col_data || !rows->col_data[src])) return fail(KHIP_E_INVALID, "value source column");
+      if (n && q.varr[c] && (!rows->col_null || !rows->col_null[src]))
+        return fail(KHIP_E_INVALID, "an ARRAY value column needs col_null (the list's length lives in its null bytes)");
       ncol = std::max(ncol, src + 1);
       ctype[src] = q.vtype[c];
       used[src] = true;
@@ -1152,9 +1304,10 @@ khip_status khip_sink_encode(khip_sink* s, const khip_sink_rows* rows, khip_sink
     r.tomb = (const uint8_t*)p;
     for (int c = 0; c < ncol; c++) {
       if (!used[c] || !rows->col_data[c]) continue;
-      KHIP_TRY(sk_stage(s, s->st_col[c], rows->col_data[c], (size_t)n * (ctype[c] == KHIP_TYPE_INT32 ? 4 : 8), &p));
+      const size_t ne = (size_t)n * (size_t)std::max(s->src_len[c], 1);  // ARRAY: n x L elements and null bytes
+      KHIP_TRY(sk_stage(s, s->st_col[c], rows->col_data[c], ne * (ctype[c] == KHIP_TYPE_INT32 ? 4 : 8), &p));
       r.col[c] = p;
-      KHIP_TRY(sk_stage(s, s->st_null[c], rows->col_null ? rows->col_null[c] : nullptr, (size_t)n, &p));
+      KHIP_TRY(sk_stage(s, s->st_null[c], rows->col_null ? rows->col_null[c] : nullptr, ne, &p));
       r.cnull[c] = (const uint8_t*)p;
     }
   } else if (rows->mem != KHIP_MEM_HOST && rows->mem != KHIP_MEM_DEVICE) {
@@ -1180,8 +1333,8 @@ khip_status khip_sink_encode(khip_sink* s, const khip_sink_rows* rows, khip_sink
   if (n) {
     KHIP_TRY(s->tsum.ensure((size_t)(2 * (nT + 1)) * 8));
     int64_t* ts = s->tsum.as<int64_t>();
-    hipLaunchKernelGGL(k_sink_measure, dim3((unsigned)nT), dim3(256), 0, s->stream, s->dq.as<SinkParams>(), r, n, kfix, nT,
-                       koff, voff, ts);
+    hipLaunchKernelGGL(s->has_arr ? k_sink_measure<true> : k_sink_measure<false>, dim3((unsigned)nT), dim3(256), 0, s->stream,
+                       s->dq.as<SinkParams>(), r, n, kfix, nT, koff, voff, ts);
     KHIP_TRY_HIP(hipGetLastError());
     int64_t tk = 0, tv = 0;
     if (!kfix) KHIP_TRY(sk_scan(s, s->bsum, ts, nT, &tk, false));
@@ -1212,8 +1365,8 @@ khip_status khip_sink_encode(khip_sink* s, const khip_sink_rows* rows, khip_sink
   }
   if (n) {
     const int kwords = kfix && q.ktype[0] == KHIP_TYPE_INT64 && ((uintptr_t)kb & 7) == 0 ? kfix / 8 : 0;
-    hipLaunchKernelGGL(k_sink_write, dim3((unsigned)nT), dim3(256), 0, s->stream, s->dq.as<SinkParams>(), r, n, kfix,
-                       kwords, nT, s->tsum.as<int64_t>(), koff, kb, voff, vb, vn);
+    hipLaunchKernelGGL(s->has_arr ? k_sink_write_arr : k_sink_write, dim3((unsigned)nT), dim3(256), 0, s->stream,
+                       s->dq.as<SinkParams>(), r, n, kfix, kwords, nT, s->tsum.as<int64_t>(), koff, kb, voff, vb, vn);
     KHIP_TRY_HIP(hipGetLastError());
   }
   if (!dev_out) {

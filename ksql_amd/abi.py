@@ -1079,6 +1079,9 @@ class SerdeHandle:
                "row_valid": np.unpackbits(dget(b.row_valid, nb, np.uint8), bitorder="little")[:n].astype(bool)}
         if b.key_i64:
             res["key"] = dget(b.key_i64, n, np.int64)
+        if b.key_offsets:  # STRING keys: the records' own key bytes, passed through
+            res["key_offsets"] = dget(b.key_offsets, n + 1, np.int64)
+            res["key_bytes"] = dget(b.key_bytes, int(res["key_offsets"][n]), np.uint8)
         cols, valid = [], []
         for c, t in enumerate(out_types):
             cols.append(dget(b.col_data[c], n, NP_TYPE[TYPE[t]] if t != "STRING" else np.int64))

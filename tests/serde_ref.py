@@ -87,6 +87,14 @@ def wrap(v, bits):
     return v - (1 << bits) if v >> (bits - 1) else v
 
 
+def int_to_double(v):
+    """BigInteger.doubleValue(): correctly rounded, Infinity past the largest finite double."""
+    try:
+        return float(v)
+    except OverflowError:
+        return float("-inf") if v < 0 else float("inf")
+
+
 def coerce_text(s, t):
     if t == "INT32":
         return parse_int(s, 32)
@@ -200,7 +208,7 @@ def decode_value(fmt, fields, raw, delim=","):
         elif isinstance(v, str):
             out[name] = coerce_text(v, t)
         elif isinstance(v, int):
-            out[name] = wrap(v, 32) if t == "INT32" else (wrap(v, 64) if t == "INT64" else float(v))
+            out[name] = wrap(v, 32) if t == "INT32" else (wrap(v, 64) if t == "INT64" else int_to_double(v))
         else:
             raise Err("unexpected JSON value")
     return out

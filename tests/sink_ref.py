@@ -202,8 +202,9 @@ def kafka_bytes(typ, v):
     raise ValueError(typ)
 
 
-def encode_key(fmt, cols, vals):
-    """cols: [(name, type)], vals: python values (never null: a null group-by value drops the row)."""
+def encode_key(fmt, cols, vals, delim=","):
+    """cols: [(name, type)], vals: python values (never null: a null group-by value drops the row).
+    delim: the DELIMITED format's delimiter (KEY_DELIMITER): it joins the fields and enters the quoting rule."""
     if fmt == "KAFKA":
         assert len(cols) == 1
         return kafka_bytes(cols[0][1], vals[0])
@@ -212,7 +213,7 @@ def encode_key(fmt, cols, vals):
             return json_value(cols[0][1], vals[0]).encode()
         return ("{" + ",".join(json_string(n) + ":" + json_value(t, v) for (n, t), v in zip(cols, vals)) + "}").encode()
     if fmt == "DELIMITED":
-        return ",".join(csv_field(t, v, i == 0) for i, ((n, t), v) in enumerate(zip(cols, vals))).encode()
+        return delim.join(csv_field(t, v, i == 0, delim) for i, ((n, t), v) in enumerate(zip(cols, vals))).encode()
     raise ValueError(fmt)
 
 
@@ -224,8 +225,8 @@ def window_suffix(kind, ws, we):
     return b""
 
 
-def encode_value(fmt, cols, vals, tombstone=False):
-    """cols: [(name, type)]; returns bytes or None (null value)."""
+def encode_value(fmt, cols, vals, tombstone=False, delim=","):
+    """cols: [(name, type)]; returns bytes or None (null value).  delim: as in encode_key (VALUE_DELIMITER)."""
     if tombstone:
         return None
     if fmt == "KAFKA":
@@ -234,7 +235,7 @@ def encode_value(fmt, cols, vals, tombstone=False):
     if fmt == "JSON":
         return ("{" + ",".join(json_string(n) + ":" + json_value(t, v) for (n, t), v in zip(cols, vals)) + "}").encode()
     if fmt == "DELIMITED":
-        return ",".join(csv_field(t, v, i == 0) for i, ((n, t), v) in enumerate(zip(cols, vals))).encode()
+        return delim.join(csv_field(t, v, i == 0, delim) for i, ((n, t), v) in enumerate(zip(cols, vals))).encode()
     raise ValueError(fmt)
 
 

@@ -110,3 +110,32 @@ def test_known_differences(checker):
     assert float(halfway + "0" * 2000 + "1") == 1.0000000000000002  # Java / Python: rounds up
     assert checker(["d 0x1p3", "d " + halfway + "0" * 2000 + "1"]) == ["err", "err"]
     assert checker(["d " + halfway + "0" * 1300 + "1"]) == ["ok %d" % bits(1.0000000000000002)]  # within the bound
+
+
+# ---- which texts the decode kernel defers to its big-integer pass (k_serde_fix)
+
+def test_halfway_texts_defer(checker):
+    """java_parse_double with big_ok = false, the decode kernel's call: every text of the halfway
+    generator needs the big-integer step, and with it the value is Python's.  The exceptions are
+    arithmetic, not the parser's, and all belong to 1e23: the midpoint above the double 1e23 is the
+    decimal 1e23 itself, whose digits past the 19th are all zero, so nothing is cut off; and for the
+    text one digit below it (twenty-three nines) the 19-digit prefix's successor is that same tie,
+    which rounds to even, to the double the prefix rounds to.  One digit up defers."""
+    import format_cases as fc
+    pool = fc.halfway_pool()
+    direct = {s + t for s in ("", "-") for t in ("1" + "0" * 23, "9" * 23)}
+    assert direct <= {t for t, _ in pool}
+    assert checker(["b " + t for t, _ in pool]) == ["direct" if t in direct else "defer" for t, _ in pool]
+    got = checker(["d " + t for t, _ in pool])
+    assert got == ["ok %d" % bits(v) for _, v in pool]
+    assert checker(["b 1.5", "b 12345678901234567890123", "b x"]) == ["direct", "direct", "err"]
+
+
+@pytest.mark.parametrize("fmt", ["DELIMITED", "JSON"])
+def test_grow_batch_overflows_the_first_fix_list(checker, fmt):
+    """The precondition of the GPU test of the fix list's growth: the batch holds at least 1025
+    deferring fields (the list starts with 1024 entries)."""
+    import format_cases as fc
+    texts = fc.grow_batch_deferring_texts(fmt)
+    assert len(texts) == 2 * fc.GROW_N
+    assert checker(["b " + t for t in texts]).count("defer") >= 1025

@@ -3,9 +3,13 @@ Double.toString digits against Python's shortest round-trip repr (which agrees w
 specification except where Java prefers a closer two-digit decimal for the smallest subnormals,
 e.g. Double.MIN_VALUE = "4.9E-324"), the layout switches at 1e-3 and 1e7, and the key / value
 formats on hand-written examples taken from the QTT expected records."""
+import json
 import math
+import os
 import random
 import struct
+
+import pytest
 
 import sink_ref
 
@@ -54,3 +58,45 @@ def test_formats():
     assert sink_ref.csv_field("STRING", "#x") == '"#x"'
     assert sink_ref.csv_field("STRING", "x ") == '"x "'
     assert sink_ref.csv_field("STRING", 'a"b') == '"a""b"'
+
+
+# ---- delimiters other than ','
+
+DELIM_CASES = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                                          "delimited_delimiters.json")))["cases"]
+
+
+def test_fixture_all_numeric_output_with_its_delimiter():
+    """The reference's "0-1" (two INT columns, value_delimiter '-'), and the other cases' outputs from
+    their input fields: joined with the output delimiter, nothing quoted."""
+    case = DELIM_CASES[0]
+    assert case["delimiter_out"] == "-" and case["outputs"] == ["0-1"]
+    cols = [tuple(c) for c in case["columns"]]
+    assert sink_ref.encode_value("DELIMITED", cols, [0, 1], delim="-") == b"0-1"
+    assert sink_ref.encode_key("DELIMITED", cols, [0, 1], delim="-") == b"0-1"
+    for case in DELIM_CASES[1:]:
+        cols = [tuple(c) for c in case["columns"]]
+        for text, want in zip(case["inputs"], case["outputs"]):
+            vals = [p if t == "STRING" else int(p) for (n, t), p in zip(cols, text.split(case["delimiter_in"]))]
+            assert sink_ref.encode_value("DELIMITED", cols, vals, delim=case["delimiter_out"]) == want.encode()
+
+
+# (type, value, printed text) and per delimiter the texts commons-csv's MINIMAL rule quotes: the ones
+# holding the delimiter.  A digit, '-', '.', 'E', 'I' and 'N' are all above '#', no text ends <= ' ',
+# so nothing else about a printed number asks for quotes.
+QUOTING_NUMBERS = [("INT32", -5, "-5"), ("INT64", 100, "100"), ("INT64", 7, "7"), ("DOUBLE", 1.5, "1.5"),
+                   ("DOUBLE", -2.25, "-2.25"), ("DOUBLE", 1.0e10, "1.0E10"), ("DOUBLE", float("nan"), "NaN"),
+                   ("DOUBLE", float("inf"), "Infinity"), ("DOUBLE", float("-inf"), "-Infinity")]
+QUOTED_UNDER = {"-": {"-5", "-2.25", "-Infinity"}, ".": {"1.5", "-2.25", "1.0E10"}, "E": {"1.0E10"},
+                "0": {"100", "1.0E10"}, "\t": set(), " ": set(), ",": set(), "|": set()}
+
+
+@pytest.mark.parametrize("delim", list(QUOTED_UNDER), ids=[repr(d) for d in QUOTED_UNDER])
+def test_number_quoting_by_delimiter(delim):
+    for first in (True, False):
+        for typ, v, text in QUOTING_NUMBERS:
+            want = '"%s"' % text if text in QUOTED_UNDER[delim] else text
+            assert sink_ref.csv_field(typ, v, first, delim) == want, (typ, v, first)
+    cols = [(str(i), t) for i, (t, _, _) in enumerate(QUOTING_NUMBERS)]
+    want = delim.join('"%s"' % x if x in QUOTED_UNDER[delim] else x for _, _, x in QUOTING_NUMBERS).encode()
+    assert sink_ref.encode_value("DELIMITED", cols, [v for _, v, _ in QUOTING_NUMBERS], delim=delim) == want

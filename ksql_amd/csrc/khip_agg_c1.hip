@@ -2942,22 +2942,9 @@ khip_status c1_push(khip_agg* a, int64_t n, const C1In& in, int64_t* tot, bool* 
       const uint32_t* wk = (pass == 0 && !subs0) ? nullptr : s.work.as<uint32_t>();
       const int64_t nwork = wk ? (int64_t)r.work.size() : g.P;
       KHIP_TRY(c1_launch_merge(a, g, m, pass, wk, nwork, dbg));
-      const int nl = pass == 0 ? g.P : (int)r.plist.size();
-      hipLaunchKernelGGL(k_part_commit, dim3(ceil_div(std::max(nl, 1), 256)), dim3(256), 0, a->stream,
-                         pass == 0 ? (const int64_t*)g.ci : (const int64_t*)nullptr, g.P, s.pbase.as<int64_t>(),
-                         s.prn.as<uint32_t>(), pass == 0 ? nullptr : s.work.as<uint32_t>() + r.work.size(), nl,
-                         s.sel.as<uint8_t>(), s.cnt.as<int64_t>(), s.newcnt.as<unsigned long long>(),
-                         s.fail.as<uint8_t>(), s.ctr.as<unsigned long long>(), s.hcnt.as<unsigned long long>(),
-                         s.hnew.as<unsigned long long>());
-      KHIP_TRY_HIP(hipGetLastError());
-      if (pass == 0) {
-        ev_record_part(a, 3);
-        hipLaunchKernelGGL(k_part_stats, dim3(1), dim3(256), 0, a->stream, s.tpart.as<int64_t>(), g.nT,
-                           s.closed_ctr.as<unsigned long long>(), a->stream_time.as<int64_t>(),
-                           s.ctr.as<unsigned long long>());
-        KHIP_TRY_HIP(hipMemcpyAsync(pi->c1info, g.ci, CI_N * 8, hipMemcpyDeviceToHost, a->stream));
-      }
-      KHIP_TRY_HIP(hipMemcpyAsync(pi->ctr, s.ctr.p, CTR_COPIED * 8, hipMemcpyDeviceToHost, a->stream));
+      KHIP_TRY(part_pass_commit(a, pass, r, pass == 0 ? (const int64_t*)g.ci : (const int64_t*)nullptr,
+                                s.prn.as<uint32_t>(), s.closed_ctr.as<unsigned long long>(), g.nT));
+      if (pass == 0) KHIP_TRY_HIP(hipMemcpyAsync(pi->c1info, g.ci, CI_N * 8, hipMemcpyDeviceToHost, a->stream));
       // the closed store's rows after this pass (closed rows leave in the pass that writes their
       // item): read with the counters, no second round trip
       KHIP_TRY_HIP(hipMemcpyAsync(&pi->closed_n, s.closed_ctr.p, 8, hipMemcpyDeviceToHost, a->stream));
@@ -2984,11 +2971,7 @@ khip_status c1_push(khip_agg* a, int64_t n, const C1In& in, int64_t* tot, bool* 
       if (c2[CTR_NEED] & C1_FATAL)  // (cannot happen: the store holds every live row)
         return fail(KHIP_E_DEVICE, "the closed store's capacity would be exceeded by a merge's closed rows");
       added_total += (int64_t)c2[CTR_ADDED];
-      host_fail.clear();
-      if (c2[CTR_FAILED] != 0) {
-        host_fail.resize(g.P);
-        KHIP_TRY_HIP(hipMemcpy(host_fail.data(), s.fail.p, g.P, hipMemcpyDeviceToHost));
-      }
+      KHIP_TRY(part_pass_failed(a, &host_fail));
 #ifdef KHIP_TUNING
       if (knob("KHIP_C1_TRACE", 0) != 0) {  // one line per pass: the tests' witness that a push was retried
         int64_t nsub, ft, fr;

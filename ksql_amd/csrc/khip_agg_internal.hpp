@@ -589,7 +589,10 @@ struct InitWords {
 constexpr int PINFO_CTR_WORDS = 13, PINFO_CI_WORDS = 24;  // = CTR_COPIED, CI_N (khip_part.hpp asserts it)
 struct PushInfo {
   // device to host
-  int64_t wr[6];                             // k_part_wrange's wr[0..6) (part_push, read after the pass-0 sync)
+  // k_part_wrange writes nine words; the host copies the first six (window-index base, identity
+  // fits, event-time min / max, merge accepted, time base) and part_push reads wr[4] after the
+  // pass-0 sync.  wr[6..9) (R8 key base, rowtime-delta bits, half-range flag) are for kernels only.
+  int64_t wr[6];
   unsigned long long ctr[PINFO_CTR_WORDS];   // the counter block after a pass (CTR_*)
   int64_t c1info[PINFO_CI_WORDS];            // c1_push: the pipeline's c1info after pass 0 (CI_*)
   unsigned long long closed_n;               // c1_push: the closed store's rows after a pass
@@ -608,7 +611,7 @@ struct PartState {
   int H_eff = 0;          // max groups placed in LDS before the partition is retried
   int nwords = 3;         // u64 words per group actually used (key, ws, rowtime, state)
   int lds_bytes = 0;
-  DevBuf pbase, R, ctr, counts;
+  DevBuf pbase, ctr, counts;
   DevBuf buf[2];          // region storage: P x cmax rows x sw words, double buffered
   DevBuf sel, cnt, newcnt, fail;  // per partition: buffer select, rows, rows being written, flags
   DevBuf hist, tilemax, tilemin, tileprefix, tpart, scan_tmp;

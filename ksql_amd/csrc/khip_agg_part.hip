@@ -11,15 +11,29 @@
 //   k_scan_blocks    exclusive prefix max of tile maxima (stream time before each tile)
 //   k_part_colsum / k_part_colbase / k_scan_excl / k_part_colprefix
 //                    column prefix sums → each (tile, partition) chunk's output offset
+//   k_part_wrange    the push's window range and event-time span → wr[]: the device's choice of
+//                    aggregate kernel and record format (R12 / R8), read by every later kernel
 //   k_part_scatter   in-tile stream time (block scan), late test, first applied window,
-//                    record → its partition's contiguous range (LDS cursors), SoA
+//                    record → its partition's contiguous range (LDS cursors, or bin-ordered
+//                    through an LDS stage), AoS
+//   k_part_scatter_w / k_part_scatter_r8
+//                    the tiles of staged 32-byte records / of 8-byte R8 records (512 threads)
+//   k_part_refine / k_part_refine_r8
+//                    two-level scatter (P >= 2048): pass-A buckets → partitions
+//   k_part_merge     persistent workgroups walk the partitions: the records' deltas in a delta-only
+//                    LDS table (one plane per op), then merged with the resident rows on write-out
+//   k_part_merge_c1  its lean form for COUNT(*) alone, one window per record (R12 / R8 records)
 //   k_part_agg       one workgroup per partition: load the partition's resident groups
 //                    (compact rows) into an LDS hash table, apply its records (window
-//                    fan-out, LDS atomics), write the compacted rows to the other buffer
+//                    fan-out, LDS atomics), write the compacted rows to the other buffer;
+//                    runs what the merges decline (window range, span, TOPK)
 //   k_part_commit    flip the partition's buffer, publish its row count
+//   k_part_stats     the push's statistics → the counter block
 // A partition whose groups overflow the LDS table (or its region) writes nothing and is
 // retried with 2x sub-passes (groups split by hash bits) / a grown region — exact, since
 // its previous rows are untouched in the other buffer.
+// Host side: part_push = part_plan (every host-known decision of the push, PartGeo) + one
+// function per stage above; c1_push (khip_agg_c1.hip) shares the per-pass steps.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -3499,8 +3513,6 @@ static int part_ceil_log2(int64_t v) {
 
 khip_status part_init(khip_agg* a, int64_t hint) {
   PartState& s = a->part;
-  const int nwords = 3 + (int)(a->ap.n_ops > 0 ? 0 : 0);
-  (void)nwords;
   // words used = highest word index + 1 (rows are padded to a->sw)
   int used = 3;
   for (int o = 0; o < a->ap.n_ops; o++)  // (a TOPK op: its whole slot span)
@@ -3587,7 +3599,6 @@ khip_status part_init(khip_agg* a, int64_t hint) {
   KHIP_TRY(s.cnt.ensure(s.P * 8));
   KHIP_TRY(s.newcnt.ensure(s.P * 8));
   KHIP_TRY(s.pbase.ensure((s.P + 1) * 8));
-  KHIP_TRY(s.R.ensure((s.P + 1) * 8));
   {
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, a->device) == hipSuccess && ncu > 0)
@@ -3619,7 +3630,7 @@ void part_release(khip_agg* a) {
                     &s.tilemax, &s.tilemin, &s.tilekr,
                     &s.tileprefix, &s.tpart, &s.scan_tmp, &s.srec, &s.work,
                     &s.c1rc, &s.c1rp, &s.c1ro, &s.c1scan, &s.c1ci, &s.c1bb, &s.c1seg, &s.c1info, &s.prn, &s.c1vq,
-                    &s.pbase, &s.R, &s.ctr, &s.counts};
+                    &s.pbase, &s.ctr, &s.counts};
   for (DevBuf* b : bufs) b->release();
 }
 
@@ -3658,8 +3669,8 @@ khip_status part_reset(khip_agg* a) {
   return KHIP_OK;
 }
 
-static PartAggParams part_params(khip_agg* a) {
-  PartState& s = a->part;
+static PartAggParams part_params(const khip_agg* a) {
+  const PartState& s = a->part;
   PartAggParams q{};
   q.windowed = a->windowed;
   q.nwords = s.nwords;
@@ -3756,7 +3767,6 @@ static khip_status part_split(khip_agg* a) {
   KHIP_TRY_HIP(hipMemsetAsync(s.hnew.p, 0, P2 * 8, a->stream));
   s.hvalid = false;
   KHIP_TRY(s.pbase.ensure((s.P + 1) * 8));
-  KHIP_TRY(s.R.ensure((s.P + 1) * 8));
   return KHIP_OK;
 }
 
@@ -3848,55 +3858,78 @@ void part_push_epilogue(khip_agg* a, int64_t closed_now, int64_t added, int64_t*
   tot[P_NEW] += added;
 }
 
-// One push slice (n < 2^31).  tot[] receives the P_* counters.
-// Shuffled rows (khip_agg_push_shuffled) through the value pipeline, read where they lie; *done =
-// false when the pipeline does not apply or declined the push (the caller unpacks the rows and
-// runs the general path, which then skips the pipeline as after any decline).
-// supplied: KHIP_TIME_SUPPLIED, the rows carry their stream-time word (the scatter reads it there).
-khip_status part_push_rows(khip_agg* a, int64_t n, const RowsIn& ri, int key_col, int64_t* tot, bool* done,
-                           bool supplied) {
+// A pass's tail, after its aggregate / merge kernel: commit (gate: the device's go-ahead word block on
+// pass 0, prn: the pipelines' records per partition, both may be null), the push's statistics
+// after pass 0 (evictions only happen there; closed_ctr null: unwindowed), the counters → host.
+// The caller adds its own copies and synchronises the stream.
+khip_status part_pass_commit(khip_agg* a, int pass, const RetryPlan& r, const int64_t* gate, const uint32_t* prn,
+                             const unsigned long long* closed_ctr, int64_t nT) {
   PartState& s = a->part;
-  *done = false;
-  while (s.log2P < SPLIT_P_LOG2 && a->occ - s.closed_n > s.P * (int64_t)s.H_eff / 2) KHIP_TRY(part_split(a));
-  s.last_c1 = false;
-  int vcol = -1;
-  if (s.c1_skip > 0 || !c1v_eligible(a, n, &vcol)) return KHIP_OK;
-  RowsIn r = ri;
-  r.vword = vcol == key_col ? 0 : 2 + vcol - (vcol > key_col ? 1 : 0);
-  r.vbit = vcol;
-  bool declined = false;
-  // st_at only selects the stream-time scatter here (never read as a column: ROWS reads the word)
-  const int64_t* st_flag = supplied ? (const int64_t*)ri.rows : nullptr;
-  KHIP_TRY(c1_push(a, n, C1In{nullptr, nullptr, nullptr, nullptr, st_flag, nullptr, vcol, &r}, tot, &declined));
-  if (a->profile) (declined ? a->times.c1_declined : a->times.c1_pushes)++;
-  if (declined) s.c1_skip = 8;
-  *done = !declined;
+  const int P = (int)s.P, nl = pass == 0 ? P : (int)r.plist.size();
+  hipLaunchKernelGGL(k_part_commit, dim3(ceil_div(std::max(nl, 1), 256)), dim3(256), 0, a->stream, gate, P,
+                     s.pbase.as<int64_t>(), prn, pass == 0 ? nullptr : s.work.as<uint32_t>() + r.work.size(), nl,
+                     s.sel.as<uint8_t>(), s.cnt.as<int64_t>(), s.newcnt.as<unsigned long long>(),
+                     s.fail.as<uint8_t>(), s.ctr.as<unsigned long long>(), s.hcnt.as<unsigned long long>(),
+                     s.hnew.as<unsigned long long>());
+  KHIP_TRY_HIP(hipGetLastError());
+  if (pass == 0) {
+    ev_record_part(a, 3);
+    hipLaunchKernelGGL(k_part_stats, dim3(1), dim3(256), 0, a->stream, s.tpart.as<int64_t>(), nT, closed_ctr,
+                       a->stream_time.as<int64_t>(), s.ctr.as<unsigned long long>());
+  }
+  KHIP_TRY_HIP(hipMemcpyAsync(s.info()->ctr, s.ctr.p, CTR_COPIED * 8, hipMemcpyDeviceToHost, a->stream));
   return KHIP_OK;
 }
 
-khip_status part_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t* ts, const uint8_t* kv,
-                      const uint8_t* rv, const ColPtrs& cols, int64_t* tot, const int64_t* st_at) {
+// After the pass's sync: the partitions' fail[] bytes when the pass failed some (else none).
+khip_status part_pass_failed(khip_agg* a, std::vector<uint8_t>* host_fail) {
   PartState& s = a->part;
-  // keep the resident groups per partition well inside the LDS table (split = exact re-layout)
-  // live groups only: closed (evicted) windows live in the flat store, not in the LDS tables
-  while (s.log2P < SPLIT_P_LOG2 && a->occ - s.closed_n > s.P * (int64_t)s.H_eff / 2) KHIP_TRY(part_split(a));
-  // the windowed COUNT(*) pipeline (khip_agg_c1.hip) when it applies; a push it declines (a tile
-  // that may hold late records, a ts span or key range too wide) runs the general path below, and
-  // the next few pushes go straight there
-  s.last_c1 = false;
-  int vcol = -1;
-  if (s.c1_skip > 0) {
-    s.c1_skip--;
-  } else if (c1_eligible(a, n) || c1v_eligible(a, n, &vcol)) {
-    // COUNT(*) alone: 8-byte records; one argument column: 16-byte value records
-    const ColPtrs* vc = vcol >= 0 ? &cols : nullptr;
-    bool declined = false;
-    KHIP_TRY(c1_push(a, n, C1In{keys, ts, kv, rv, st_at, vc, vcol, nullptr}, tot, &declined));
-    if (a->profile) (declined ? a->times.c1_declined : a->times.c1_pushes)++;
-    if (!declined) return KHIP_OK;
-    s.c1_skip = 8;
-  }
-  const int P = (int)s.P;
+  host_fail->clear();
+  if (s.info()->ctr[CTR_FAILED] == 0) return KHIP_OK;
+  host_fail->resize(s.P);
+  KHIP_TRY_HIP(hipMemcpy(host_fail->data(), s.fail.p, s.P, hipMemcpyDeviceToHost));
+  return KHIP_OK;
+}
+
+// ---- the general path: one plan per push (part_plan), then the stages that take it
+
+// One push's input columns.
+struct PartIn {
+  const int64_t *keys, *ts;
+  const uint8_t *kv, *rv;
+  const ColPtrs* cols;
+  const int64_t* st_at;
+};
+
+// Every host-known decision of a general-path push (part_plan), handed to every stage.
+struct PartGeo {
+  int64_t n, tile, nT, ncap;  // records, records per tile, tiles, rows of the record buffers
+  int P, TC, pad;
+  bool lvl2, narrow;    // two-level scatter; 16-byte records (rw 2)
+  int fbits, B, nbins;  // pass B's partition bits, pass A's buckets, the scatter's bins (B or P)
+  int U, wu, r8u;       // records per thread per step as instantiated: k_part_scatter, its 32-byte stage, R8
+  bool stage, wstage, r8k, wk;  // the scatter's LDS stages (16- / 32-byte records); the R8 and wide kernels
+  // two-level only: the refine's stages, records per thread per step, tiles per block, blocks per
+  // bucket, grid
+  bool rstage, rwstage;
+  int ru, G, refine_mode;
+  int64_t ng, ref_grid;
+  bool merge_allow, r12_ok, r12_merge, cnt1, c1_plan, r8_allow;
+  int mt, c1h, c1au, merge_wpc;  // merge threads, k_part_merge_c1's log2 table and AU, merge workgroups per CU
+  int fan, pane, merge_dbg;      // MergeParams' fan, pane and dbg
+  size_t hist_lds, scat_lds, sw_lds, s8_lds, ref_lds, r8_lds, merge_lds;  // LDS bytes per launch
+  PartAggParams q0;  // k_part_agg's parameters (a pass refreshes cmax and chg); adv, fd and size for the others
+  int64_t close0;    // the stream time before the push - grace (INT64_MIN: no window is closed yet)
+  bool probe, trace;
+};
+
+// The plan of a push of n records, in dependency order: no HIP call, no allocation, no state written.
+// Every knob that picks a path is read here, once per push.
+static PartGeo part_plan(const khip_agg* a, int64_t n) {
+  const PartState& s = a->part;
+  PartGeo g{};
+  g.n = n;
+  g.P = (int)s.P;
   // records per thread per tile: PT_ITEMS, fewer when that leaves fewer tiles than CUs (one
   // workgroup per tile: C1's 1M records were 16 tiles on 256 CUs — k_part_scatter_r8 87 -> 11 us and
   // k_part_hist 39 -> 14 us at 4 items, profiles/r06/ab/c1_tile_items.txt) and the per-tile
@@ -3905,34 +3938,159 @@ khip_status part_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t
   while (items > 4 && ceil_div(n, (int64_t)PT_THREADS * items) < s.n_cu &&
          ceil_div(n, (int64_t)PT_THREADS * (items >> 1)) * s.P <= (1LL << 21))
     items >>= 1;
-  const int64_t tile = (int64_t)PT_THREADS * knob("KHIP_TILE_ITEMS", items);
-  const int pad = (int)knob("KHIP_PAD", 0);
-  const int64_t nT = ceil_div(n, tile);
-  const int TC = (int)std::min<int64_t>(nT, TC_MAX);
-  KHIP_TRY(s.hist.ensure((size_t)nT * P * 4));
-  KHIP_TRY(s.tilemax.ensure(nT * 8));
-  KHIP_TRY(s.tilemin.ensure(nT * 8));
-  KHIP_TRY(s.tilekr.ensure(nT * 16));
-  KHIP_TRY(s.tileprefix.ensure(nT * 8));
-  KHIP_TRY(s.tpart.ensure(nT * 8 * T_NPART));
-  KHIP_TRY(s.scan_tmp.ensure((size_t)TC * P * 8));
-  const int64_t ncap = pad ? n + 3 * (int64_t)P * nT : n;  // padded runs
+  g.tile = (int64_t)PT_THREADS * knob("KHIP_TILE_ITEMS", items);
+  g.pad = (int)knob("KHIP_PAD", 0);
+  g.nT = ceil_div(n, g.tile);
+  g.TC = (int)std::min<int64_t>(g.nT, TC_MAX);
+  g.ncap = g.pad ? n + 3 * (int64_t)g.P * g.nT : n;  // padded runs
   // two-level scatter (pass A: B = P >> fbits buckets; pass B: partitions inside a bucket)
   // once single-level runs get short (P large against the tile)
-  const bool lvl2 = !pad && s.log2P >= 11 && knob("KHIP_SCATTER2", 1) != 0;
-  const int fbits = lvl2 ? s.log2P - s.log2P / 2 : 0;
-  const int B = P >> fbits;
-  if (s.scat_cap < ncap) {
-    const int64_t n = ncap;
-    KHIP_TRY(s.srec.ensure((size_t)(n + 1) * s.rw * 8));  // AoS records (+1: dummy store target)
-    s.scat_cap = ncap;
+  g.lvl2 = !g.pad && s.log2P >= 11 && knob("KHIP_SCATTER2", 1) != 0;
+  g.fbits = g.lvl2 ? s.log2P - s.log2P / 2 : 0;
+  g.B = g.P >> g.fbits;
+  g.nbins = g.lvl2 ? g.B : g.P;  // the LDS stages' bins (stage_step): B buckets (two-level) or P
+  g.narrow = s.rw == 2;
+  g.q0 = part_params(a);
+  g.close0 = (a->windowed && a->host_stream_time >= 0) ? a->host_stream_time - a->grace : INT64_MIN;
+  // which aggregate kernel pass 0 runs, as far as the host knows (k_part_wrange has the last word)
+  // (a TOPK / TOPKDISTINCT handle: k_part_agg only — the merges have no plane form of the chain)
+  g.merge_allow = s.mH >= 256 && knob("KHIP_MERGE", 1) != 0 && !a->has_topk;
+  const int64_t r12_mode = knob("KHIP_R12", 1);  // 1: 12-byte records end to end; 2: pass A only
+  g.r12_ok = g.narrow && !g.pad && g.merge_allow && r12_mode != 0;
+  g.r12_merge = g.r12_ok && (r12_mode == 1 || !g.lvl2);  // what k_part_merge reads
+  // COUNT(*) alone: row = [key, ws, rowtime, count] (sw 4), one u32 delta plane
+  // and (key hash, ts) records with one window each (TUMBLING or no window: no meta word)
+  g.cnt1 = a->ap.n_ops == 1 && a->ap.ops[0].kind == OP_INC && a->ap.ops[0].word == 3 && a->sw == 4 && s.rw == 2 &&
+           a->desc.window_kind != KHIP_WINDOW_HOPPING;
+  g.mt = (int)knob("KHIP_MERGE_THREADS", 512);
+  // the lean COUNT(*) merge reads R8 records too
+  g.c1_plan = g.cnt1 && g.r12_merge && a->windowed && g.q0.adv <= (int64_t)1 << 31 && g.mt >= 512 &&
+              knob("KHIP_MERGE_C1", 1) != 0;
+  g.r8_allow = g.c1_plan && knob("KHIP_R8", 1) != 0;
+  g.c1h = (int)knob("KHIP_C1_LOG2H", 12);  // the lean COUNT(*) merge's table
+  g.c1au = (int)knob("KHIP_C1_AU", 6);
+  g.merge_wpc = (int)knob("KHIP_MERGE_WG_PER_CU", g.c1_plan ? 2 : (g.mt >= 512 ? KHIP_MG_WPE / 2 : KHIP_MG_WPE));
+  g.merge_lds = g.c1_plan ? (size_t)((1 << g.c1h) + 64) * 16 : (size_t)s.m_lds;
+  g.fan = a->windowed ? (int32_t)std::min<int64_t>((g.q0.size + g.q0.adv - 1) / g.q0.adv, 1 << 20) : 1;
+  g.pane = a->windowed && g.fan > 1 && g.fan <= MG_FB && g.q0.size % g.q0.adv == 0 && knob("KHIP_PANES", 1) ? 1 : 0;
+  g.merge_dbg = (int)knob("KHIP_MERGE_DEBUG", 0);
+  // the scatter: the instantiated records per thread per step
+  const int U = (int)knob("KHIP_SCATTER_U", g.narrow ? 8 : 16);
+  g.U = U >= 16 ? 16 : (U >= 8 ? 8 : (g.narrow && U >= 6 ? 6 : 4));
+  const bool stage_knob = knob("KHIP_STAGE", 1) != 0, wstage_knob = knob("KHIP_WSTAGE", 1) != 0;
+  g.stage = g.narrow && !g.pad && g.nbins <= PT_THREADS && g.U <= 8 && stage_knob;
+  // 32-byte records (key hash, ts, meta / value words) through the LDS stage too (2 x 1024 per step)
+  g.wstage = !g.narrow && s.rw == 4 && !g.pad && g.nbins <= PT_THREADS && wstage_knob;
+  g.wu = g.U >= 16 ? 4 : 2;  // k_part_scatter's WU: staged 32-byte records per thread per step
+  // R8 records (decided on the device) through k_part_scatter_r8 / k_part_refine_r8
+  g.r8k = g.r8_allow && g.stage && g.U == 8 && g.nbins <= R8_NT && (!g.lvl2 || (1 << g.fbits) <= R8_NT) &&
+          knob("KHIP_R8K", 1) != 0;
+  // 32-byte records through k_part_scatter_w (host-known)
+  g.wk = g.wstage && g.nbins <= W_NT && knob("KHIP_WK", 1) != 0;
+  g.r8u = knob("KHIP_R8_U", 8) >= 8 ? 8 : 4;  // R8 records per thread per staged step
+  g.hist_lds = (size_t)g.P * 4;
+  g.scat_lds = g.stage ? stage_lds_bytes(g.nbins, g.U * PT_THREADS / 2)
+                       : (g.wstage ? stage_lds_bytes(g.nbins, 2 * g.wu * PT_THREADS)
+                                   : (g.lvl2 ? (size_t)g.B * 4 : g.hist_lds));
+  g.sw_lds = stage_lds_bytes(g.nbins, 2 * g.wu * W_NT);
+  g.s8_lds = stage_r8_lds_bytes(g.nbins, g.r8u * R8_NT);
+  if (g.lvl2) {  // the refine
+    const int F = 1 << g.fbits;
+    const int64_t per_blk = knob("KHIP_REFINE_RECS", 8192);  // measured: 8K records per block (1 KB runs) beat 32K
+    g.G = (int)std::max<int64_t>(1, std::min<int64_t>(g.nT, per_blk * g.B / g.tile));
+    g.ng = ceil_div(g.nT, g.G);
+    g.rstage = s.rw == 2 && F <= PT_THREADS && stage_knob;
+    g.rwstage = s.rw == 4 && F <= PT_THREADS && wstage_knob;
+    g.ru = g.rwstage ? (knob("KHIP_REFINE_WU", 4) >= 4 ? 4 : 2)  // 32-byte records per thread per step
+                     : (knob("KHIP_REFINE_U", 8) >= 8 ? 8 : 4);   // records per thread per staged step
+    g.ref_lds = g.rstage ? stage_lds_bytes(F, g.ru * PT_THREADS / 2)
+                         : (g.rwstage ? stage_lds_bytes(F, 2 * g.ru * PT_THREADS) : 0);
+    g.ref_grid = (g.r8k && g.rstage) ? std::min<int64_t>(g.B * g.ng, 2 * s.n_cu) : g.B * g.ng;
+    g.r8_lds = stage_r8_lds_bytes(F, g.r8u * R8_NT);
+    g.refine_mode = (int)knob("KHIP_REFINE_MODE", 0);
   }
-  if (lvl2) {
-    KHIP_TRY(s.srecA.ensure((size_t)(n + 1) * s.rw * 8));
-    KHIP_TRY(s.hcoarse.ensure((size_t)nT * B * 4));
-    KHIP_TRY(s.scan_tmpB.ensure((size_t)TC * B * 8));
-    KHIP_TRY(s.RB.ensure((size_t)(B + 1) * 8));
+  g.probe = knob("KHIP_AGG_PROBE", 0) != 0;  // per-workgroup phase timestamps of pass 0 (wall clock, 100 MHz) → stderr
+  g.trace = knob("KHIP_PART_TRACE", 0) != 0;
+  return g;
+}
+
+// Scratch for the plan's geometry (grown, never shrunk: no allocation once the shapes repeat).
+static khip_status part_scratch(khip_agg* a, const PartGeo& g) {
+  PartState& s = a->part;
+  KHIP_TRY(s.hist.ensure((size_t)g.nT * g.P * 4));
+  KHIP_TRY(s.tilemax.ensure(g.nT * 8));
+  KHIP_TRY(s.tilemin.ensure(g.nT * 8));
+  KHIP_TRY(s.tilekr.ensure(g.nT * 16));
+  KHIP_TRY(s.tileprefix.ensure(g.nT * 8));
+  KHIP_TRY(s.tpart.ensure(g.nT * 8 * T_NPART));
+  KHIP_TRY(s.scan_tmp.ensure((size_t)g.TC * g.P * 8));
+  if (s.scat_cap < g.ncap) {
+    KHIP_TRY(s.srec.ensure((size_t)(g.ncap + 1) * s.rw * 8));  // AoS records (+1: dummy store target)
+    s.scat_cap = g.ncap;
   }
+  if (g.lvl2) {
+    KHIP_TRY(s.srecA.ensure((size_t)(g.ncap + 1) * s.rw * 8));
+    KHIP_TRY(s.hcoarse.ensure((size_t)g.nT * g.B * 4));
+    KHIP_TRY(s.scan_tmpB.ensure((size_t)g.TC * g.B * 8));
+    KHIP_TRY(s.RB.ensure((size_t)(g.B + 1) * 8));
+  }
+  KHIP_TRY(s.wr.ensure(128));
+  KHIP_TRY(s.res.ensure(16));
+  KHIP_TRY(s.closed_ctr.ensure(8));
+  return KHIP_OK;
+}
+
+// 1. histogram + tile stream-time maxima; the window range of the push (packed identity) and its
+//    event-time span → the pinned block: they pick the aggregate kernel (k_part_merge needs the
+//    identity and a span below 2^31 ms)
+static khip_status part_histogram(khip_agg* a, const PartIn& in, const PartGeo& g) {
+  PartState& s = a->part;
+  if (g.hist_lds > 64 * 1024)
+    hipFuncSetAttribute((const void*)k_part_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.hist_lds);
+  ev_record_part(a, 0);
+  hipLaunchKernelGGL(k_part_hist, dim3(g.nT), dim3(PT_THREADS), g.hist_lds, a->stream, in.keys, in.ts, in.kv, in.rv, g.n,
+                     g.tile, s.log2P, g.pad, g.nT, s.hist.as<uint32_t>(), s.tilemax.as<int64_t>(),
+                     s.tilemin.as<int64_t>(), s.tpart.as<int64_t>(), g.fbits,
+                     g.lvl2 ? s.hcoarse.as<uint32_t>() : (uint32_t*)nullptr, s.tilekr.as<int64_t>(), in.st_at);
+  hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, a->stream, s.tilemax.as<int64_t>(), g.nT,
+                     s.tileprefix.as<int64_t>(), a->stream_time.as<int64_t>());
+  hipLaunchKernelGGL(k_part_wrange, dim3(1), dim3(1024), 0, a->stream, s.tilemin.as<int64_t>(), s.tilemax.as<int64_t>(),
+                     g.nT, a->windowed, a->desc.size_ms, g.q0.adv, g.q0.fd, g.close0, s.log2P, s.res_fresh ? 1 : 0,
+                     (a->desc.flags & KHIP_FLAG_PART_CLAIM) ? 0 : 1, g.merge_allow ? 1 : 0, s.res.as<int64_t>(),
+                     s.wr.as<int64_t>(), s.ctr.as<unsigned long long>(),
+                     a->windowed ? s.closed_ctr.as<unsigned long long>() : (unsigned long long*)nullptr,
+                     (unsigned long long)s.closed_n, s.tilekr.as<int64_t>(), g.r8_allow ? 1 : 0);
+  s.res_fresh = false;
+  KHIP_TRY_HIP(hipMemcpyAsync(s.info()->wr, s.wr.p, sizeof(s.info()->wr), hipMemcpyDeviceToHost, a->stream));
+  return KHIP_OK;
+}
+
+// 2. offsets
+static void part_offsets(khip_agg* a, const PartGeo& g) {
+  PartState& s = a->part;
+  const int P = g.P, B = g.B, TC = g.TC;
+  hipLaunchKernelGGL(k_part_colsum, dim3(ceil_div(P, 256), TC), dim3(256), 0, a->stream, s.hist.as<uint32_t>(), g.nT, P,
+                     TC, s.scan_tmp.as<int64_t>());
+  hipLaunchKernelGGL(k_part_colbase, dim3(ceil_div(P, 256)), dim3(256), 0, a->stream, s.scan_tmp.as<int64_t>(), P, TC,
+                     s.pbase.as<int64_t>());
+  hipLaunchKernelGGL(k_part_pscan, dim3(1), dim3(1024), 0, a->stream, s.pbase.as<int64_t>(), (int64_t)P);
+  hipLaunchKernelGGL(k_part_colprefix, dim3(ceil_div(P, 256), TC), dim3(256), 0, a->stream, s.hist.as<uint32_t>(), g.nT,
+                     P, TC, s.scan_tmp.as<int64_t>(), s.pbase.as<int64_t>(), 1);
+  if (g.lvl2) {  // bucket b's region = its partitions' regions [pbase[b << fbits], pbase[(b + 1) << fbits])
+    hipLaunchKernelGGL(k_part_colsum, dim3(ceil_div(B, 256), TC), dim3(256), 0, a->stream, s.hcoarse.as<uint32_t>(),
+                       g.nT, B, TC, s.scan_tmpB.as<int64_t>());
+    hipLaunchKernelGGL(k_part_colbase, dim3(ceil_div(B, 256)), dim3(256), 0, a->stream, s.scan_tmpB.as<int64_t>(), B,
+                       TC, s.RB.as<int64_t>());
+    hipLaunchKernelGGL(k_part_colprefix, dim3(ceil_div(B, 256), TC), dim3(256), 0, a->stream, s.hcoarse.as<uint32_t>(),
+                       g.nT, B, TC, s.scan_tmpB.as<int64_t>(), s.pbase.as<int64_t>(), 1 << g.fbits);
+  }
+  ev_record_part(a, 1);
+}
+
+// 3. scatter (12-byte records for k_part_merge when the layout is narrow: r12_ok, decided on the
+//    device by wr[4]); the wide staged tiles and the R8 tiles have kernels of their own
+static khip_status part_scatter(khip_agg* a, const PartIn& in, const PartGeo& g) {
+  PartState& s = a->part;
   ColTypes ct{};
   for (int c = 0; c < MAX_COLS; c++) ct.t[c] = a->ap.col_type[c];
   RecLayout L{};
@@ -3944,343 +4102,353 @@ khip_status part_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t
     L.col_word[c] = s.col_word[c];
     if (s.col_word[c] >= 0) L.word_col[s.col_word[c]] = (int8_t)c;
   }
-  const size_t hist_lds = (size_t)P * 4;
-  if (hist_lds > 64 * 1024)
-    hipFuncSetAttribute((const void*)k_part_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_lds);
-  // 1. histogram + tile stream-time maxima
-  ev_record_part(a, 0);
-  hipLaunchKernelGGL(k_part_hist, dim3(nT), dim3(PT_THREADS), hist_lds, a->stream, keys, ts, kv, rv, n, tile, s.log2P,
-                     pad, nT,
-                     s.hist.as<uint32_t>(), s.tilemax.as<int64_t>(), s.tilemin.as<int64_t>(), s.tpart.as<int64_t>(),
-                     fbits, lvl2 ? s.hcoarse.as<uint32_t>() : (uint32_t*)nullptr, s.tilekr.as<int64_t>(), st_at);
-  hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, a->stream, s.tilemax.as<int64_t>(), nT,
-                     s.tileprefix.as<int64_t>(), a->stream_time.as<int64_t>());
-  // window range of the push (packed identity) and its event-time span → host: they pick the
-  // aggregate kernel (k_part_merge needs the identity and a span below 2^31 ms)
-  const PartAggParams q0 = part_params(a);
-  const int64_t close0 = (a->windowed && a->host_stream_time >= 0) ? a->host_stream_time - a->grace : INT64_MIN;
-  KHIP_TRY(s.wr.ensure(128));
-  KHIP_TRY(s.res.ensure(16));
-  KHIP_TRY(s.closed_ctr.ensure(8));
-  // (a TOPK / TOPKDISTINCT handle: k_part_agg only — the merges have no plane form of the chain)
-  const bool merge_allow = s.mH >= 256 && knob("KHIP_MERGE", 1) != 0 && !a->has_topk;
-  // which merge kernel pass 0 runs (host-known): the lean COUNT(*) merge reads R8 records too
-  const bool narrow = s.rw == 2;
-  const int64_t r12_mode = knob("KHIP_R12", 1);  // 1: 12-byte records end to end; 2: pass A only
-  const bool r12_ok = narrow && !pad && merge_allow && r12_mode != 0;
-  const bool r12_merge = r12_ok && (r12_mode == 1 || !lvl2);  // what k_part_merge reads
-  // COUNT(*) alone: row = [key, ws, rowtime, count] (sw 4), one u32 delta plane
-  // and (key hash, ts) records with one window each (TUMBLING or no window: no meta word)
-  const bool cnt1 = a->ap.n_ops == 1 && a->ap.ops[0].kind == OP_INC && a->ap.ops[0].word == 3 && a->sw == 4 &&
-                    s.rw == 2 && a->desc.window_kind != KHIP_WINDOW_HOPPING;
-  const int mt = (int)knob("KHIP_MERGE_THREADS", 512);
-  const bool c1_plan = cnt1 && r12_merge && a->windowed && q0.adv <= (int64_t)1 << 31 && mt >= 512 &&
-                       knob("KHIP_MERGE_C1", 1) != 0;
-  const bool r8_allow = c1_plan && knob("KHIP_R8", 1) != 0;
-  hipLaunchKernelGGL(k_part_wrange, dim3(1), dim3(1024), 0, a->stream, s.tilemin.as<int64_t>(), s.tilemax.as<int64_t>(),
-                     nT, a->windowed, a->desc.size_ms, q0.adv, q0.fd, close0, s.log2P, s.res_fresh ? 1 : 0,
-                     (a->desc.flags & KHIP_FLAG_PART_CLAIM) ? 0 : 1, merge_allow ? 1 : 0, s.res.as<int64_t>(),
-                     s.wr.as<int64_t>(), s.ctr.as<unsigned long long>(),
-                     a->windowed ? s.closed_ctr.as<unsigned long long>() : (unsigned long long*)nullptr,
-                     (unsigned long long)s.closed_n, s.tilekr.as<int64_t>(), r8_allow ? 1 : 0);
-  s.res_fresh = false;
-  int64_t* pin = s.info()->wr;  // wr[0..6), read after the pass-0 sync
-  KHIP_TRY_HIP(hipMemcpyAsync(pin, s.wr.p, sizeof(s.info()->wr), hipMemcpyDeviceToHost, a->stream));
-  // 2. offsets
-  hipLaunchKernelGGL(k_part_colsum, dim3(ceil_div(P, 256), TC), dim3(256), 0, a->stream, s.hist.as<uint32_t>(), nT, P,
-                     TC, s.scan_tmp.as<int64_t>());
-  hipLaunchKernelGGL(k_part_colbase, dim3(ceil_div(P, 256)), dim3(256), 0, a->stream, s.scan_tmp.as<int64_t>(), P, TC,
-                     s.pbase.as<int64_t>());
-  hipLaunchKernelGGL(k_part_pscan, dim3(1), dim3(1024), 0, a->stream, s.pbase.as<int64_t>(), (int64_t)P);
-  hipLaunchKernelGGL(k_part_colprefix, dim3(ceil_div(P, 256), TC), dim3(256), 0, a->stream, s.hist.as<uint32_t>(), nT,
-                     P, TC, s.scan_tmp.as<int64_t>(), s.pbase.as<int64_t>(), 1);
-  if (lvl2) {  // bucket b's region = its partitions' regions [pbase[b << fbits], pbase[(b + 1) << fbits])
-    hipLaunchKernelGGL(k_part_colsum, dim3(ceil_div(B, 256), TC), dim3(256), 0, a->stream, s.hcoarse.as<uint32_t>(), nT,
-                       B, TC, s.scan_tmpB.as<int64_t>());
-    hipLaunchKernelGGL(k_part_colbase, dim3(ceil_div(B, 256)), dim3(256), 0, a->stream, s.scan_tmpB.as<int64_t>(), B, TC,
-                       s.RB.as<int64_t>());
-    hipLaunchKernelGGL(k_part_colprefix, dim3(ceil_div(B, 256), TC), dim3(256), 0, a->stream, s.hcoarse.as<uint32_t>(),
-                       nT, B, TC, s.scan_tmpB.as<int64_t>(), s.pbase.as<int64_t>(), 1 << fbits);
-  }
-  ev_record_part(a, 1);
-  // 3. scatter (12-byte records for k_part_merge when the layout is narrow: r12_ok, decided
-  //    on the device by wr[4])
-  const int U = (int)knob("KHIP_SCATTER_U", narrow ? 8 : 16);
-  auto scat = narrow ? (U >= 16 ? k_part_scatter<16, true> : (U >= 8 ? k_part_scatter<8, true> : (U >= 6 ? k_part_scatter<6, true> : k_part_scatter<4, true>)))
-                     : (U >= 16 ? k_part_scatter<16, false> : (U >= 8 ? k_part_scatter<8, false> : k_part_scatter<4, false>));
-  // narrow records leave through the LDS stage (stage_step): bins = B buckets (two-level) or P
-  const int nbins = lvl2 ? B : P;
-  const int Ut = U >= 16 ? 16 : (U >= 8 ? 8 : (narrow && U >= 6 ? 6 : 4));  // the instantiated records per thread per step
-  const bool stage = narrow && !pad && nbins <= PT_THREADS && Ut <= 8 && knob("KHIP_STAGE", 1) != 0;
-  // 32-byte records (key hash, ts, meta / value words) through the LDS stage too (2 x 1024 per step)
-  const bool wstage = !narrow && s.rw == 4 && !pad && nbins <= PT_THREADS && knob("KHIP_WSTAGE", 1) != 0;
-  const int wu = Ut >= 16 ? 4 : 2;  // k_part_scatter's WU: staged 32-byte records per thread per step
-  // R8 records (decided on the device) through k_part_scatter_r8 / k_part_refine_r8
-  const bool r8k = r8_allow && stage && Ut == 8 && nbins <= R8_NT && (!lvl2 || (1 << fbits) <= R8_NT) &&
-                   knob("KHIP_R8K", 1) != 0;
-  // 32-byte records through k_part_scatter_w (host-known)
-  const bool wk = wstage && nbins <= W_NT && knob("KHIP_WK", 1) != 0;
-  const size_t scat_lds = stage ? stage_lds_bytes(nbins, Ut * PT_THREADS / 2)
-                                : (wstage ? stage_lds_bytes(nbins, 2 * wu * PT_THREADS)
-                                          : (lvl2 ? (size_t)B * 4 : hist_lds));
-  if (scat_lds > 64 * 1024)
-    hipFuncSetAttribute((const void*)scat, hipFuncAttributeMaxDynamicSharedMemorySize, (int)scat_lds);
-  hipLaunchKernelGGL(scat, dim3(nT), dim3(PT_THREADS), scat_lds, a->stream, keys, ts, kv, rv,
-                     cols, a->ap.n_cols, ct, n, tile, s.log2P - fbits, pad, nT,
-                     lvl2 ? s.hcoarse.as<uint32_t>() : s.hist.as<uint32_t>(), s.pbase.as<int64_t>(),
-                     s.tileprefix.as<int64_t>(),
-                     s.tilemax.as<int64_t>(), s.tilemin.as<int64_t>(), a->windowed, a->desc.size_ms,
-                     a->windowed ? a->desc.advance_ms : 1, make_fastdiv(a->windowed ? a->desc.advance_ms : 1),
-                     a->grace, L, lvl2 ? s.srecA.as<uint64_t>() : s.srec.as<uint64_t>(), ncap,
-                     s.tpart.as<int64_t>(), s.wr.as<int64_t>(), r12_ok ? 1 : 0, (stage || wstage) ? 1 : 0,
-                     (r8k || wk) ? 1 : 0, st_at);
+  // what the three kernels share: the bins' counts, the output records, the window arithmetic
+  uint32_t* hist = g.lvl2 ? s.hcoarse.as<uint32_t>() : s.hist.as<uint32_t>();
+  uint64_t* out = g.lvl2 ? s.srecA.as<uint64_t>() : s.srec.as<uint64_t>();
+  int64_t *tprefix = s.tileprefix.as<int64_t>(), *tmax = s.tilemax.as<int64_t>(), *tmin = s.tilemin.as<int64_t>();
+  const int bits = s.log2P - g.fbits, n_cols = a->ap.n_cols;
+  const int64_t size = a->desc.size_ms, adv = g.q0.adv;
+  auto scat = g.narrow ? (g.U == 16 ? k_part_scatter<16, true> : (g.U == 8 ? k_part_scatter<8, true> : (g.U == 6 ? k_part_scatter<6, true> : k_part_scatter<4, true>)))
+                       : (g.U == 16 ? k_part_scatter<16, false> : (g.U == 8 ? k_part_scatter<8, false> : k_part_scatter<4, false>));
+  if (g.scat_lds > 64 * 1024)
+    hipFuncSetAttribute((const void*)scat, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.scat_lds);
+  hipLaunchKernelGGL(scat, dim3(g.nT), dim3(PT_THREADS), g.scat_lds, a->stream, in.keys, in.ts, in.kv, in.rv, *in.cols,
+                     n_cols, ct, g.n, g.tile, bits, g.pad, g.nT, hist, s.pbase.as<int64_t>(), tprefix, tmax, tmin,
+                     a->windowed, size, adv, g.q0.fd, a->grace, L, out, g.ncap, s.tpart.as<int64_t>(),
+                     s.wr.as<int64_t>(), g.r12_ok ? 1 : 0, (g.stage || g.wstage) ? 1 : 0, (g.r8k || g.wk) ? 1 : 0,
+                     in.st_at);
   KHIP_TRY_HIP(hipGetLastError());
-  if (wk) {  // the wide staged tiles
-    auto sw_ = wu >= 4 ? k_part_scatter_w<4, W_NT> : k_part_scatter_w<2, W_NT>;
-    const size_t sw_lds = stage_lds_bytes(nbins, 2 * wu * W_NT);
-    if (sw_lds > 64 * 1024) hipFuncSetAttribute((const void*)sw_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sw_lds);
-    hipLaunchKernelGGL(sw_, dim3(nT), dim3(W_NT), sw_lds, a->stream, keys, ts, kv, rv, cols, a->ap.n_cols, ct, n, tile,
-                       s.log2P - fbits, nT, lvl2 ? s.hcoarse.as<uint32_t>() : s.hist.as<uint32_t>(),
-                       s.tileprefix.as<int64_t>(), s.tilemax.as<int64_t>(), s.tilemin.as<int64_t>(), a->windowed,
-                       a->desc.size_ms, a->windowed ? a->desc.advance_ms : 1,
-                       make_fastdiv(a->windowed ? a->desc.advance_ms : 1), a->grace, L,
-                       lvl2 ? s.srecA.as<uint64_t>() : s.srec.as<uint64_t>(), s.tpart.as<int64_t>());
+  if (g.wk) {  // the wide staged tiles
+    auto sw_ = g.wu >= 4 ? k_part_scatter_w<4, W_NT> : k_part_scatter_w<2, W_NT>;
+    if (g.sw_lds > 64 * 1024)
+      hipFuncSetAttribute((const void*)sw_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.sw_lds);
+    hipLaunchKernelGGL(sw_, dim3(g.nT), dim3(W_NT), g.sw_lds, a->stream, in.keys, in.ts, in.kv, in.rv, *in.cols, n_cols,
+                       ct, g.n, g.tile, bits, g.nT, hist, tprefix, tmax, tmin, a->windowed, size, adv, g.q0.fd,
+                       a->grace, L, out, s.tpart.as<int64_t>());
     KHIP_TRY_HIP(hipGetLastError());
   }
-  const int r8u = knob("KHIP_R8_U", 8) >= 8 ? 8 : 4;  // R8 records per thread per staged step
-  if (r8k) {  // the R8 tiles (exits at once unless k_part_wrange chose R8)
-    auto s8 = r8u == 8 ? k_part_scatter_r8<8, R8_NT> : k_part_scatter_r8<4, R8_NT>;
-    const size_t s8_lds = stage_r8_lds_bytes(nbins, r8u * R8_NT);
-    if (s8_lds > 64 * 1024) hipFuncSetAttribute((const void*)s8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s8_lds);
-    hipLaunchKernelGGL(s8, dim3(nT), dim3(R8_NT), s8_lds, a->stream, keys, ts, kv, rv, n, tile, s.log2P - fbits, nT,
-                       lvl2 ? s.hcoarse.as<uint32_t>() : s.hist.as<uint32_t>(), s.tileprefix.as<int64_t>(),
-                       s.tilemax.as<int64_t>(), s.tilemin.as<int64_t>(), a->windowed, a->desc.size_ms,
-                       a->windowed ? a->desc.advance_ms : 1, make_fastdiv(a->windowed ? a->desc.advance_ms : 1),
-                       a->grace, lvl2 ? s.srecA.as<uint64_t>() : s.srec.as<uint64_t>(), s.tpart.as<int64_t>(),
-                       s.wr.as<int64_t>());
+  if (g.r8k) {  // the R8 tiles (exits at once unless k_part_wrange chose R8)
+    auto s8 = g.r8u == 8 ? k_part_scatter_r8<8, R8_NT> : k_part_scatter_r8<4, R8_NT>;
+    if (g.s8_lds > 64 * 1024)
+      hipFuncSetAttribute((const void*)s8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.s8_lds);
+    hipLaunchKernelGGL(s8, dim3(g.nT), dim3(R8_NT), g.s8_lds, a->stream, in.keys, in.ts, in.kv, in.rv, g.n, g.tile, bits,
+                       g.nT, hist, tprefix, tmax, tmin, a->windowed, size, adv, g.q0.fd, a->grace, out,
+                       s.tpart.as<int64_t>(), s.wr.as<int64_t>());
     KHIP_TRY_HIP(hipGetLastError());
   }
-  if (lvl2) {
-    const int64_t per_blk = knob("KHIP_REFINE_RECS", 8192);  // measured: 8K records per block (1 KB runs) beat 32K
-    const int G = (int)std::max<int64_t>(1, std::min<int64_t>(nT, per_blk * B / tile));
-    const int64_t ng = ceil_div(nT, G);
-    void (*ref)(const uint64_t*, const uint32_t*, const uint32_t*, const int64_t*, int64_t, int, int, int, int64_t,
-                uint64_t*, int, const int64_t*, int, int, int);
-    switch (s.rw) {
-      case 2: ref = k_part_refine<2>; break;
-      case 4: ref = k_part_refine<4>; break;
-      case 6: ref = k_part_refine<6>; break;
-      case 8: ref = k_part_refine<8>; break;
-      case 10: ref = k_part_refine<10>; break;
-      default: ref = k_part_refine<12>; break;
-    }
-    const bool rstage = s.rw == 2 && (1 << fbits) <= PT_THREADS && knob("KHIP_STAGE", 1) != 0;
-    const bool rwstage = s.rw == 4 && (1 << fbits) <= PT_THREADS && knob("KHIP_WSTAGE", 1) != 0;
-    const int ru = rwstage ? (knob("KHIP_REFINE_WU", 4) >= 4 ? 4 : 2)  // 32-byte records per thread per step
-                           : (knob("KHIP_REFINE_U", 8) >= 8 ? 8 : 4);   // records per thread per staged step
-    const size_t ref_lds = rstage ? stage_lds_bytes(1 << fbits, ru * PT_THREADS / 2)
-                                  : (rwstage ? stage_lds_bytes(1 << fbits, 2 * ru * PT_THREADS) : 0);
-    if (ref_lds) hipFuncSetAttribute((const void*)ref, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ref_lds);
-    const int64_t ref_grid = (r8k && rstage) ? std::min<int64_t>(B * ng, 2 * s.n_cu) : B * ng;
-    hipLaunchKernelGGL(ref, dim3((unsigned)ref_grid), dim3(PT_THREADS), ref_lds, a->stream, s.srecA.as<uint64_t>(),
-                       s.hcoarse.as<uint32_t>(), s.hist.as<uint32_t>(), s.pbase.as<int64_t>(), nT, G, s.log2P, fbits,
-                       ncap, s.srec.as<uint64_t>(), (int)knob("KHIP_REFINE_MODE", 0), s.wr.as<int64_t>(),
-                       r12_ok ? (r12_merge ? 1 : 2) : 0, (rstage || rwstage) ? ru : 0, (r8k && rstage) ? 1 : 0);
-    KHIP_TRY_HIP(hipGetLastError());
-    if (r8k && rstage) {
-      auto r8 = r8u == 8 ? k_part_refine_r8<8, R8_NT> : k_part_refine_r8<4, R8_NT>;
-      const size_t r8_lds = stage_r8_lds_bytes(1 << fbits, r8u * R8_NT);
-      if (r8_lds > 64 * 1024) hipFuncSetAttribute((const void*)r8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r8_lds);
-      hipLaunchKernelGGL(r8, dim3((unsigned)(B * ng)), dim3(R8_NT), r8_lds, a->stream, s.srecA.as<uint64_t>(),
-                         s.hcoarse.as<uint32_t>(), s.hist.as<uint32_t>(), s.pbase.as<int64_t>(), nT, G, s.log2P, fbits,
-                         s.srec.as<uint64_t>(), s.wr.as<int64_t>());
-      KHIP_TRY_HIP(hipGetLastError());
-    }
+  return KHIP_OK;
+}
+
+// 3b. two-level: pass-A buckets → partitions (and the R8 form, which exits unless R8 was chosen)
+static khip_status part_refine(khip_agg* a, const PartGeo& g) {
+  PartState& s = a->part;
+  void (*ref)(const uint64_t*, const uint32_t*, const uint32_t*, const int64_t*, int64_t, int, int, int, int64_t,
+              uint64_t*, int, const int64_t*, int, int, int);
+  switch (s.rw) {
+    case 2: ref = k_part_refine<2>; break;
+    case 4: ref = k_part_refine<4>; break;
+    case 6: ref = k_part_refine<6>; break;
+    case 8: ref = k_part_refine<8>; break;
+    case 10: ref = k_part_refine<10>; break;
+    default: ref = k_part_refine<12>; break;
   }
-  ev_record_part(a, 2);
-  // 4. aggregate partitions (+ retries).  k_part_merge is launched speculatively (it and its
-  //    commit exit when k_part_wrange declined it); pass 0 is then redone with k_part_agg.
-  bool merge = merge_allow;
+  const bool r8 = g.r8k && g.rstage;
+  if (g.ref_lds) hipFuncSetAttribute((const void*)ref, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.ref_lds);
+  hipLaunchKernelGGL(ref, dim3((unsigned)g.ref_grid), dim3(PT_THREADS), g.ref_lds, a->stream, s.srecA.as<uint64_t>(),
+                     s.hcoarse.as<uint32_t>(), s.hist.as<uint32_t>(), s.pbase.as<int64_t>(), g.nT, g.G, s.log2P, g.fbits,
+                     g.ncap, s.srec.as<uint64_t>(), g.refine_mode, s.wr.as<int64_t>(),
+                     g.r12_ok ? (g.r12_merge ? 1 : 2) : 0, (g.rstage || g.rwstage) ? g.ru : 0, r8 ? 1 : 0);
+  KHIP_TRY_HIP(hipGetLastError());
+  if (r8) {
+    auto k8 = g.r8u == 8 ? k_part_refine_r8<8, R8_NT> : k_part_refine_r8<4, R8_NT>;
+    if (g.r8_lds > 64 * 1024)
+      hipFuncSetAttribute((const void*)k8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.r8_lds);
+    hipLaunchKernelGGL(k8, dim3((unsigned)(g.B * g.ng)), dim3(R8_NT), g.r8_lds, a->stream, s.srecA.as<uint64_t>(),
+                       s.hcoarse.as<uint32_t>(), s.hist.as<uint32_t>(), s.pbase.as<int64_t>(), g.nT, g.G, s.log2P, g.fbits,
+                       s.srec.as<uint64_t>(), s.wr.as<int64_t>());
+    KHIP_TRY_HIP(hipGetLastError());
+  }
+  return KHIP_OK;
+}
+
+// The aggregate kernels' parameters, built once per push; a pass refreshes cmax and chg (a
+// retry's regrow moves them).
+struct PartAggQ {
+  PartAggParams q;
+  MergeParams mq;
+  C1Params cq;
+};
+
+static MergeParams part_merge_params(const khip_agg* a, const PartGeo& g) {
+  const PartState& s = a->part;
+  const PartAggParams& q0 = g.q0;
   MergeParams mq{};
-  if (merge) {
-    mq.windowed = a->windowed;
-    mq.sw = a->sw;
-    mq.nwords = s.nwords;
-    mq.H = s.mH;
-    mq.rw = s.rw;
-    mq.meta_word = s.meta_word;
-    mq.log2P = s.log2P;
-    mq.n_ops = a->ap.n_ops;
-    mq.size = q0.size;
-    mq.adv = q0.adv;
-    mq.fd = q0.fd;
-    mq.div32 = a->windowed && q0.adv <= (int64_t)1 << 31 ? 1 : 0;
-    mq.fd32 = make_fastdiv32((uint32_t)(mq.div32 ? q0.adv : 1));
-    for (int c = 0; c < MAX_COLS; c++) {
-      mq.col_word[c] = s.col_word[c];
-      mq.col_type[c] = a->ap.col_type[c];
-    }
-    for (int o = 0; o < a->ap.n_ops; o++) {
-      mq.ops[o] = a->ap.ops[o];
-      mq.plane_off[o] = s.plane_off[o];
-      mq.plane_w64[o] = s.plane_w64[o];
-    }
-    mq.rt_off = s.rt_off;
-    mq.list_off = s.m_list_off;
-    mq.fan = a->windowed ? (int32_t)std::min<int64_t>((q0.size + q0.adv - 1) / q0.adv, 1 << 20) : 1;
-    mq.pane = a->windowed && mq.fan > 1 && mq.fan <= MG_FB && q0.size % q0.adv == 0 && knob("KHIP_PANES", 1) ? 1 : 0;
-    mq.lds_bytes = s.m_lds;
-    mq.init = a->init;
-    mq.having = a->having;
-    mq.dbg = (int32_t)knob("KHIP_MERGE_DEBUG", 0);
-    mq.r12 = r12_merge ? 1 : 0;
-    mq.chg = a->changelog ? a->chg.as<uint8_t>() : nullptr;
+  mq.windowed = a->windowed;
+  mq.sw = a->sw;
+  mq.nwords = s.nwords;
+  mq.H = s.mH;
+  mq.rw = s.rw;
+  mq.meta_word = s.meta_word;
+  mq.log2P = s.log2P;
+  mq.n_ops = a->ap.n_ops;
+  mq.size = q0.size;
+  mq.adv = q0.adv;
+  mq.fd = q0.fd;
+  mq.div32 = a->windowed && q0.adv <= (int64_t)1 << 31 ? 1 : 0;
+  mq.fd32 = make_fastdiv32((uint32_t)(mq.div32 ? q0.adv : 1));
+  for (int c = 0; c < MAX_COLS; c++) {
+    mq.col_word[c] = s.col_word[c];
+    mq.col_type[c] = a->ap.col_type[c];
   }
+  for (int o = 0; o < a->ap.n_ops; o++) {
+    mq.ops[o] = a->ap.ops[o];
+    mq.plane_off[o] = s.plane_off[o];
+    mq.plane_w64[o] = s.plane_w64[o];
+  }
+  mq.rt_off = s.rt_off;
+  mq.list_off = s.m_list_off;
+  mq.fan = g.fan;
+  mq.pane = g.pane;
+  mq.lds_bytes = s.m_lds;
+  mq.init = a->init;
+  mq.having = a->having;
+  mq.dbg = g.merge_dbg;
+  mq.r12 = g.r12_merge ? 1 : 0;
+  return mq;
+}
+
+static C1Params part_c1_params(const khip_agg* a, const PartGeo& g, const MergeParams& mq) {
+  C1Params cq{};
+  cq.log2P = mq.log2P;
+  cq.log2H = g.c1h;
+  cq.sw = mq.sw;
+  cq.size = mq.size;
+  cq.adv = mq.adv;
+  cq.fd = mq.fd;
+  cq.fd32 = mq.fd32;
+  cq.hv_active = a->having.active;
+  cq.hv_op = a->having.op;
+  cq.hv_i64 = a->having.i64;
+  return cq;
+}
+
+// 4. one pass's aggregate kernel over the nwork items of wk (null: one per partition): the lean
+//    COUNT(*) merge, the generic merge, or (merge = false) k_part_agg.  The merges of pass 0 are
+//    launched speculatively: they and their commit exit when k_part_wrange declined them.
+static void part_launch_agg(khip_agg* a, const PartGeo& g, const PartAggQ& k, bool merge, int pass, const uint32_t* wk,
+                            int64_t nwork, unsigned long long* dbg) {
+  PartState& s = a->part;
+  unsigned long long* ctr = s.ctr.as<unsigned long long>();
+  const int first = pass == 0 ? 1 : 0, lds = (int)g.merge_lds;
+  const int64_t grid = std::min<int64_t>(nwork, (int64_t)s.n_cu * g.merge_wpc);
+  if (merge && g.c1_plan) {
+    const int au = g.c1au;
+    // both record layouts' instantiations (R8 only when k_part_wrange may choose it)
+    for (int rm = g.r8_allow ? 1 : 0; rm >= 0; rm--) {
+      auto mk = rm ? (au >= 8 ? k_part_merge_c1<512, 8, 1> : (au >= 6 ? k_part_merge_c1<512, 6, 1> : k_part_merge_c1<512, 4, 1>))
+                   : (au >= 8 ? k_part_merge_c1<512, 8, 0> : (au >= 6 ? k_part_merge_c1<512, 6, 0> : k_part_merge_c1<512, 4, 0>));
+      hipFuncSetAttribute((const void*)mk, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      hipLaunchKernelGGL(mk, dim3(grid), dim3(512), lds, a->stream, k.cq, wk, nwork, s.pbase.as<int64_t>(),
+                         s.srec.as<uint64_t>(), first, s.buf[0].as<uint64_t>(), s.buf[1].as<uint64_t>(),
+                         s.sel.as<uint8_t>(), s.cnt.as<int64_t>(), s.newcnt.as<unsigned long long>(),
+                         s.fail.as<uint8_t>(), ctr + CTR_NEED, g.close0, s.closed.as<uint64_t>(),
+                         s.closed_ctr.as<unsigned long long>(), s.wr.as<int64_t>(), s.hnew.as<unsigned long long>(),
+                         ctr + CTR_HAVING_CLOSED, dbg);
+    }
+  } else if (merge) {
+    const bool cnt1 = g.cnt1;
+    auto mk = k.mq.r12 ? (g.mt >= 512 ? (cnt1 ? k_part_merge<true, 512, true> : k_part_merge<false, 512, true>)
+                                       : (cnt1 ? k_part_merge<true, 256, true> : k_part_merge<false, 256, true>))
+                       : (g.mt >= 512 ? (cnt1 ? k_part_merge<true, 512, false> : k_part_merge<false, 512, false>)
+                                       : (cnt1 ? k_part_merge<true, 256, false> : k_part_merge<false, 256, false>));
+    hipFuncSetAttribute((const void*)mk, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipLaunchKernelGGL(mk, dim3(grid), dim3(g.mt >= 512 ? 512 : 256), lds, a->stream, k.mq, wk, nwork,
+                       s.pbase.as<int64_t>(), s.srec.as<uint64_t>(), first, s.buf[0].as<uint64_t>(),
+                       s.buf[1].as<uint64_t>(), s.sel.as<uint8_t>(), s.cnt.as<int64_t>(),
+                       s.newcnt.as<unsigned long long>(), s.fail.as<uint8_t>(), ctr + CTR_NEED, g.close0,
+                       s.closed.as<uint64_t>(), s.closed_ctr.as<unsigned long long>(), s.wr.as<int64_t>(),
+                       s.hnew.as<unsigned long long>(), ctr + CTR_HAVING_CLOSED, dbg);
+  } else {
+    hipFuncSetAttribute((const void*)k_part_agg, hipFuncAttributeMaxDynamicSharedMemorySize, s.lds_bytes);
+    hipLaunchKernelGGL(k_part_agg, dim3(nwork), dim3(AG_THREADS), s.lds_bytes, a->stream, k.q, wk, s.pbase.as<int64_t>(),
+                       s.srec.as<uint64_t>(), first, s.buf[0].as<uint64_t>(), s.buf[1].as<uint64_t>(),
+                       s.sel.as<uint8_t>(), s.cnt.as<int64_t>(), s.newcnt.as<unsigned long long>(),
+                       s.fail.as<uint8_t>(), ctr + CTR_NEED, g.close0, s.closed.as<uint64_t>(),
+                       s.closed_ctr.as<unsigned long long>(), s.wr.as<int64_t>(), dbg);
+  }
+}
+
+// KHIP_AGG_PROBE after a merge pass: per-phase time summed over its persistent workgroups.
+static void merge_probe_report(const khip_agg* a, const PartGeo& g, const DevBuf& b) {
+  unsigned long long ph[8] = {};
+  if (hipMemcpy(ph, b.p, sizeof(ph), hipMemcpyDeviceToHost) != hipSuccess) return;
+  const double us = (double)std::min<int64_t>(g.P, 2 * a->part.n_cu) * 100.0;  // 100 MHz ticks → us per workgroup
+  if (g.c1_plan)
+    fprintf(stderr, "[merge c1 probe] per workgroup (us): item start+evict %.1f records %.1f mark+count+reserve %.1f "
+            "write %.1f\n", ph[0] / us, ph[1] / us, ph[2] / us, ph[3] / us);
+  else
+    fprintf(stderr, "[merge probe] per workgroup (us): setup %.1f evict %.1f records %.1f mark+reserve %.1f write %.1f\n",
+            ph[0] / us, ph[1] / us, ph[2] / us, ph[3] / us, ph[4] / us);
+}
+
+// One pass up to its sync: counters cleared (pass 0: k_part_wrange did), the aggregate kernel,
+// the shared tail.  *nwork = its work items; *dbg = the probe's buffer on pass 0, else null.
+static khip_status part_run_pass(khip_agg* a, const PartGeo& g, PartAggQ& k, const RetryPlan& r, bool subs0, bool merge,
+                                 int pass, DevBuf& dbgbuf, int64_t* nwork, unsigned long long** dbg) {
+  PartState& s = a->part;
+  const uint32_t* wk = (pass == 0 && !subs0) ? nullptr : s.work.as<uint32_t>();
+  *nwork = wk ? (int64_t)r.work.size() : g.P;
+  *dbg = nullptr;
+  if (g.probe && pass == 0) {
+    KHIP_TRY(dbgbuf.ensure((size_t)std::max<int64_t>(g.P, (int64_t)r.work.size()) * 6 * 8 + 64));
+    KHIP_TRY_HIP(hipMemsetAsync(dbgbuf.p, 0, dbgbuf.bytes, a->stream));
+    *dbg = dbgbuf.as<unsigned long long>();
+  }
+  k.q.cmax = k.mq.cmax = k.cq.cmax = s.cmax;
+  k.q.chg = k.mq.chg = k.cq.chg = a->changelog ? a->chg.as<uint8_t>() : nullptr;
+  if (pass > 0) KHIP_TRY_HIP(hipMemsetAsync(s.ctr.p, 0, CTR_PER_PASS * 8, a->stream));
+  part_launch_agg(a, g, k, merge, pass, wk, *nwork, *dbg);
+  KHIP_TRY(part_pass_commit(a, pass, r, (merge && pass == 0) ? s.wr.as<int64_t>() : (const int64_t*)nullptr, nullptr,
+                            a->windowed ? s.closed_ctr.as<unsigned long long>() : (const unsigned long long*)nullptr,
+                            g.nT));
+  KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
+  return KHIP_OK;
+}
+
+#ifdef KHIP_TUNING
+// KHIP_PART_TRACE=1: the push's plan; r12: 0 / 1 = the merge reads R12 / 2 = pass A only
+static void part_trace_plan(const khip_agg* a, const PartGeo& g) {
+  fprintf(stderr,
+          "[part plan] rw=%d P=%d tile=%lld nT=%lld lvl2=%d fbits=%d stage=%d wstage=%d r8k=%d wk=%d r12=%d cnt1=%d "
+          "c1_plan=%d r8_allow=%d merge_allow=%d U=%d\n",
+          a->part.rw, g.P, (long long)g.tile, (long long)g.nT, g.lvl2 ? 1 : 0, g.fbits, g.stage ? 1 : 0,
+          g.wstage ? 1 : 0, g.r8k ? 1 : 0, g.wk ? 1 : 0, g.r12_ok ? (g.r12_merge ? 1 : 2) : 0, g.cnt1 ? 1 : 0,
+          g.c1_plan ? 1 : 0, g.r8_allow ? 1 : 0, g.merge_allow ? 1 : 0, g.U);
+}
+
+// ... and one line per pass, as c1_push's [c1 trace]
+static void part_trace_pass(const khip_agg* a, const PartGeo& g, const RetryPlan& r, bool merge, int pass, bool listed,
+                            int64_t nwork, const std::vector<uint8_t>& host_fail) {
+  const PartState& s = a->part;
+  const unsigned long long* c2 = s.info()->ctr;
+  int64_t nsub, ft, fr;
+  part_retry_trace_counts(r, listed, host_fail, &nsub, &ft, &fr);
+  const int H = !merge ? s.H : (g.c1_plan ? 1 << g.c1h : s.mH);  // the kernel's LDS table (entries)
+  fprintf(stderr,
+          "[part trace] kernel=%s P=%d cmax=%lld H=%d pass=%d items=%lld sub_items=%lld failed=%llu "
+          "fail_table=%lld fail_region=%lld closed_before=%lld closed_after=%llu\n",
+          !merge ? "agg" : (g.c1_plan ? "merge_c1" : "merge"), g.P, (long long)s.cmax, H, pass, (long long)nwork,
+          (long long)nsub, c2[CTR_FAILED], (long long)ft, (long long)fr, (long long)s.closed_n,
+          a->windowed ? c2[CTR_CLOSED] : 0ULL);
+}
+#endif
+
+// Keep the resident groups per partition well inside the LDS table (split = exact re-layout).
+// Live groups only: closed (evicted) windows live in the flat store, not in the LDS tables.
+static khip_status part_split_crowded(khip_agg* a) {
+  PartState& s = a->part;
+  while (s.log2P < SPLIT_P_LOG2 && a->occ - s.closed_n > s.P * (int64_t)s.H_eff / 2) KHIP_TRY(part_split(a));
+  return KHIP_OK;
+}
+
+// A pipeline's turn at the push (khip_agg_c1.hip).  *done = false when it declined (a tile that
+// may hold late records, a ts span or key range too wide): the general path runs the push, and the
+// next few pushes go straight there.
+static khip_status part_try_pipeline(khip_agg* a, int64_t n, const C1In& in, int64_t* tot, bool* done) {
+  bool declined = false;
+  KHIP_TRY(c1_push(a, n, in, tot, &declined));
+  if (a->profile) (declined ? a->times.c1_declined : a->times.c1_pushes)++;
+  if (declined) a->part.c1_skip = 8;
+  *done = !declined;
+  return KHIP_OK;
+}
+
+// One push slice (n < 2^31).  tot[] receives the P_* counters.
+// Shuffled rows (khip_agg_push_shuffled) through the value pipeline, read where they lie; *done =
+// false when the pipeline does not apply or declined the push (the caller unpacks the rows and
+// runs the general path, which then skips the pipeline as after any decline).
+// supplied: KHIP_TIME_SUPPLIED, the rows carry their stream-time word (the scatter reads it there).
+khip_status part_push_rows(khip_agg* a, int64_t n, const RowsIn& ri, int key_col, int64_t* tot, bool* done,
+                           bool supplied) {
+  PartState& s = a->part;
+  *done = false;
+  KHIP_TRY(part_split_crowded(a));
+  s.last_c1 = false;
+  int vcol = -1;
+  if (s.c1_skip > 0 || !c1v_eligible(a, n, &vcol)) return KHIP_OK;
+  RowsIn r = ri;
+  r.vword = vcol == key_col ? 0 : 2 + vcol - (vcol > key_col ? 1 : 0);
+  r.vbit = vcol;
+  // st_at only selects the stream-time scatter here (never read as a column: ROWS reads the word)
+  const int64_t* st_flag = supplied ? (const int64_t*)ri.rows : nullptr;
+  return part_try_pipeline(a, n, C1In{nullptr, nullptr, nullptr, nullptr, st_flag, nullptr, vcol, &r}, tot, done);
+}
+
+khip_status part_push(khip_agg* a, int64_t n, const int64_t* keys, const int64_t* ts, const uint8_t* kv,
+                      const uint8_t* rv, const ColPtrs& cols, int64_t* tot, const int64_t* st_at) {
+  PartState& s = a->part;
+  KHIP_TRY(part_split_crowded(a));
+  s.last_c1 = false;
+  int vcol = -1;
+  if (s.c1_skip > 0) {
+    s.c1_skip--;
+  } else if (c1_eligible(a, n) || c1v_eligible(a, n, &vcol)) {
+    // COUNT(*) alone: 8-byte records; one argument column: 16-byte value records
+    bool done = false;
+    KHIP_TRY(part_try_pipeline(a, n, C1In{keys, ts, kv, rv, st_at, vcol >= 0 ? &cols : nullptr, vcol, nullptr}, tot,
+                               &done));
+    if (done) return KHIP_OK;
+  }
+  const PartIn in{keys, ts, kv, rv, &cols, st_at};
+  const PartGeo g = part_plan(a, n);
+#ifdef KHIP_TUNING
+  if (g.trace) part_trace_plan(a, g);
+#endif
+  KHIP_TRY(part_scratch(a, g));
+  KHIP_TRY(part_histogram(a, in, g));
+  part_offsets(a, g);
+  KHIP_TRY(part_scatter(a, in, g));
+  if (g.lvl2) KHIP_TRY(part_refine(a, g));
+  ev_record_part(a, 2);
+  // 4. aggregate partitions (+ retries: DESIGN.md (d))
+  PartAggQ k{};
+  k.q = g.q0;
+  if (g.merge_allow) k.mq = part_merge_params(a, g);
+  if (g.c1_plan) k.cq = part_c1_params(a, g, k.mq);
   if (a->windowed) KHIP_TRY(part_grow_closed(a));
-  int64_t added_total = 0;
-  std::vector<uint8_t> host_fail;
   // pass 0: one work item per partition, or its learned 2^sbits sub-passes
   RetryPlan r;
   retry_begin(r, s.psbits);
-  const std::vector<uint32_t>& work = r.work;
-  const bool subs0 = !work.empty();
+  const bool subs0 = !r.work.empty();
   if (subs0) KHIP_TRY(part_upload_plan(a, r.image));
-  // KHIP_AGG_PROBE=1: per-workgroup phase timestamps of pass 0 (wall clock, 100 MHz) → stderr
-  const bool probe = knob("KHIP_AGG_PROBE", 0) != 0;
+  const unsigned long long* c2 = s.info()->ctr;
+  std::vector<uint8_t> host_fail;
   DevBuf dbgbuf;
   unsigned long long* dbg = nullptr;
-  bool c1_ran = false;
-  const int c1h = (int)knob("KHIP_C1_LOG2H", 12);  // the lean COUNT(*) merge's table
+  int64_t added_total = 0, nwork = 0;
+  bool merge = g.merge_allow;
   for (int pass = 0;; pass++) {
-    PartAggParams q = q0;
-    dbg = nullptr;
-    if (probe && pass == 0) {
-      KHIP_TRY(dbgbuf.ensure((size_t)std::max<int64_t>(P, (int64_t)work.size()) * 6 * 8 + 64));
-      KHIP_TRY_HIP(hipMemsetAsync(dbgbuf.p, 0, dbgbuf.bytes, a->stream));
-      dbg = dbgbuf.as<unsigned long long>();
-    }
-    q.cmax = s.cmax;
-    mq.cmax = s.cmax;
-    q.chg = mq.chg = a->changelog ? a->chg.as<uint8_t>() : nullptr;  // a retry's regrow moves them
-    if (pass > 0) KHIP_TRY_HIP(hipMemsetAsync(s.ctr.p, 0, CTR_PER_PASS * 8, a->stream));  // pass 0: k_part_wrange
-    const uint32_t* wk = (pass == 0 && !subs0) ? nullptr : s.work.as<uint32_t>();
-    const int64_t nwork = (pass == 0 && !subs0) ? P : (int64_t)work.size();
-    if (merge) {
-      c1_ran = c1_plan;
-      if (c1_ran) {  // the lean COUNT(*) merge
-        const int au = (int)knob("KHIP_C1_AU", 6);
-        const int lds = ((1 << c1h) + 64) * 16;
-        // both record layouts' instantiations (R8 only when k_part_wrange may choose it)
-        for (int rm = r8_allow ? 1 : 0; rm >= 0; rm--) {
-        auto mk = rm ? (au >= 8 ? k_part_merge_c1<512, 8, 1> : (au >= 6 ? k_part_merge_c1<512, 6, 1> : k_part_merge_c1<512, 4, 1>))
-                     : (au >= 8 ? k_part_merge_c1<512, 8, 0> : (au >= 6 ? k_part_merge_c1<512, 6, 0> : k_part_merge_c1<512, 4, 0>));
-        hipFuncSetAttribute((const void*)mk, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        const int64_t grid = std::min<int64_t>(nwork, (int64_t)s.n_cu * knob("KHIP_MERGE_WG_PER_CU", 2));
-        C1Params cq{};
-        cq.log2P = mq.log2P;
-        cq.log2H = c1h;
-        cq.sw = mq.sw;
-        cq.size = mq.size;
-        cq.adv = mq.adv;
-        cq.cmax = mq.cmax;
-        cq.fd = mq.fd;
-        cq.fd32 = mq.fd32;
-        cq.chg = mq.chg;
-        cq.hv_active = a->having.active;
-        cq.hv_op = a->having.op;
-        cq.hv_i64 = a->having.i64;
-        hipLaunchKernelGGL(mk, dim3(grid), dim3(512), lds, a->stream, cq, wk, nwork, s.pbase.as<int64_t>(),
-                           s.srec.as<uint64_t>(), pass == 0 ? 1 : 0, s.buf[0].as<uint64_t>(), s.buf[1].as<uint64_t>(),
-                           s.sel.as<uint8_t>(), s.cnt.as<int64_t>(), s.newcnt.as<unsigned long long>(),
-                           s.fail.as<uint8_t>(), s.ctr.as<unsigned long long>() + CTR_NEED, close0, s.closed.as<uint64_t>(),
-                           s.closed_ctr.as<unsigned long long>(), s.wr.as<int64_t>(),
-                           s.hnew.as<unsigned long long>(), s.ctr.as<unsigned long long>() + CTR_HAVING_CLOSED, dbg);
-        }
-      } else {
-      auto mk = mq.r12 ? (mt >= 512 ? (cnt1 ? k_part_merge<true, 512, true> : k_part_merge<false, 512, true>)
-                                    : (cnt1 ? k_part_merge<true, 256, true> : k_part_merge<false, 256, true>))
-                       : (mt >= 512 ? (cnt1 ? k_part_merge<true, 512, false> : k_part_merge<false, 512, false>)
-                                    : (cnt1 ? k_part_merge<true, 256, false> : k_part_merge<false, 256, false>));
-      hipFuncSetAttribute((const void*)mk, hipFuncAttributeMaxDynamicSharedMemorySize, s.m_lds);
-      const int64_t grid = std::min<int64_t>(nwork, (int64_t)s.n_cu * knob("KHIP_MERGE_WG_PER_CU", mt >= 512 ? KHIP_MG_WPE / 2 : KHIP_MG_WPE));
-      hipLaunchKernelGGL(mk, dim3(grid), dim3(mt >= 512 ? 512 : 256), s.m_lds, a->stream, mq, wk, nwork, s.pbase.as<int64_t>(),
-                         s.srec.as<uint64_t>(), pass == 0 ? 1 : 0, s.buf[0].as<uint64_t>(), s.buf[1].as<uint64_t>(),
-                         s.sel.as<uint8_t>(), s.cnt.as<int64_t>(), s.newcnt.as<unsigned long long>(),
-                         s.fail.as<uint8_t>(), s.ctr.as<unsigned long long>() + CTR_NEED, close0, s.closed.as<uint64_t>(),
-                         s.closed_ctr.as<unsigned long long>(), s.wr.as<int64_t>(),
-                         s.hnew.as<unsigned long long>(), s.ctr.as<unsigned long long>() + CTR_HAVING_CLOSED, dbg);
-      }
-    } else {
-      hipFuncSetAttribute((const void*)k_part_agg, hipFuncAttributeMaxDynamicSharedMemorySize, s.lds_bytes);
-      hipLaunchKernelGGL(k_part_agg, dim3(nwork), dim3(AG_THREADS), s.lds_bytes, a->stream, q, wk,
-                         s.pbase.as<int64_t>(), s.srec.as<uint64_t>(), pass == 0 ? 1 : 0, s.buf[0].as<uint64_t>(),
-                         s.buf[1].as<uint64_t>(), s.sel.as<uint8_t>(), s.cnt.as<int64_t>(),
-                         s.newcnt.as<unsigned long long>(), s.fail.as<uint8_t>(),
-                         s.ctr.as<unsigned long long>() + CTR_NEED, close0, s.closed.as<uint64_t>(),
-                         s.closed_ctr.as<unsigned long long>(), s.wr.as<int64_t>(), dbg);
-    }
-    const int nl = pass == 0 ? P : (int)r.plist.size();
-    hipLaunchKernelGGL(k_part_commit, dim3(ceil_div(std::max(nl, 1), 256)), dim3(256), 0, a->stream,
-                       (merge && pass == 0) ? s.wr.as<int64_t>() : (const int64_t*)nullptr, P,
-                       s.pbase.as<int64_t>(), (const uint32_t*)nullptr,
-                       pass == 0 ? nullptr : s.work.as<uint32_t>() + work.size(), nl,
-                       s.sel.as<uint8_t>(), s.cnt.as<int64_t>(), s.newcnt.as<unsigned long long>(),
-                       s.fail.as<uint8_t>(), s.ctr.as<unsigned long long>(), s.hcnt.as<unsigned long long>(),
-                       s.hnew.as<unsigned long long>());
-    KHIP_TRY_HIP(hipGetLastError());
-    if (pass == 0) {
-      ev_record_part(a, 3);
-      hipLaunchKernelGGL(k_part_stats, dim3(1), dim3(256), 0, a->stream, s.tpart.as<int64_t>(), nT,
-                         a->windowed ? s.closed_ctr.as<unsigned long long>() : (unsigned long long*)nullptr,
-                         a->stream_time.as<int64_t>(), s.ctr.as<unsigned long long>());
-    }
-    const unsigned long long* c2 = s.info()->ctr;
-    KHIP_TRY_HIP(hipMemcpyAsync(s.info()->ctr, s.ctr.p, CTR_COPIED * 8, hipMemcpyDeviceToHost, a->stream));
-    KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
-    if (pass == 0 && merge && pin[4] == 0) {  // declined on the device: nothing was written
+    KHIP_TRY(part_run_pass(a, g, k, r, subs0, merge, pass, dbgbuf, &nwork, &dbg));
+    if (pass == 0 && merge && s.info()->wr[4] == 0) {
+      // declined on the device (the window range or the event-time span): the merge and its commit
+      // wrote nothing, pass 0 runs again with k_part_agg
       merge = false;
-      s.hvalid = false;  // k_part_agg does not maintain the HAVING counts
-      pass = -1;
-      continue;
+      s.hvalid = false;
+      KHIP_TRY(part_run_pass(a, g, k, r, subs0, merge, pass, dbgbuf, &nwork, &dbg));
     }
     added_total += (int64_t)c2[CTR_ADDED];
-    if (dbg && merge) {  // k_part_merge: per-phase time summed over its persistent workgroups
-      unsigned long long ph[8] = {};
-      if (hipMemcpy(ph, dbgbuf.p, sizeof(ph), hipMemcpyDeviceToHost) == hipSuccess) {
-        const double g = (double)std::min<int64_t>(P, 2 * s.n_cu) * 100.0;  // 100 MHz ticks → us per workgroup
-        if (c1_ran)
-          fprintf(stderr, "[merge c1 probe] per workgroup (us): item start+evict %.1f records %.1f mark+count+reserve %.1f "
-                  "write %.1f\n", ph[0] / g, ph[1] / g, ph[2] / g, ph[3] / g);
-        else
-          fprintf(stderr, "[merge probe] per workgroup (us): setup %.1f evict %.1f records %.1f mark+reserve %.1f write %.1f\n",
-                  ph[0] / g, ph[1] / g, ph[2] / g, ph[3] / g, ph[4] / g);
-      }
-    } else if (dbg) {
-      agg_probe_report(dbgbuf, (int)((pass == 0 && !subs0) ? P : (int64_t)work.size()));
-    }
-    host_fail.clear();
-    if (c2[CTR_FAILED] != 0) {
-      host_fail.resize(P);
-      KHIP_TRY_HIP(hipMemcpy(host_fail.data(), s.fail.p, P, hipMemcpyDeviceToHost));
-    }
+    if (dbg && merge) merge_probe_report(a, g, dbgbuf);
+    else if (dbg) agg_probe_report(dbgbuf, (int)nwork);
+    KHIP_TRY(part_pass_failed(a, &host_fail));
 #ifdef KHIP_TUNING
-    if (knob("KHIP_PART_TRACE", 0) != 0) {  // one line per pass, as c1_push's [c1 trace]
-      int64_t nsub, ft, fr;
-      part_retry_trace_counts(r, wk != nullptr, host_fail, &nsub, &ft, &fr);
-      const int H = !merge ? s.H : (c1_ran ? 1 << c1h : s.mH);  // the kernel's LDS table (entries)
-      fprintf(stderr,
-              "[part trace] kernel=%s P=%d cmax=%lld H=%d pass=%d items=%lld sub_items=%lld failed=%llu "
-              "fail_table=%lld fail_region=%lld closed_before=%lld closed_after=%llu\n",
-              !merge ? "agg" : (c1_ran ? "merge_c1" : "merge"), P, (long long)s.cmax, H, pass, (long long)nwork, (long long)nsub, c2[CTR_FAILED], (long long)ft, (long long)fr,
-              (long long)s.closed_n, a->windowed ? c2[CTR_CLOSED] : 0ULL);
-    }
+    if (g.trace) part_trace_pass(a, g, r, merge, pass, pass > 0 || subs0, nwork, host_fail);
 #endif
     if (c2[CTR_FAILED] == 0) break;
     // retry the failed partitions: LDS overflow → twice the sub-passes; region overflow → grow
     KHIP_TRY(part_plan_retry(a, r, pass, host_fail));
   }
   retry_learn(s.psbits, r);
-  if (!merge) s.hvalid = false;
+  if (!merge) s.hvalid = false;  // k_part_agg does not maintain the HAVING counts
   // 5. counters (k_part_stats after pass 0: evictions only happen there)
   part_push_epilogue(a, a->windowed ? (int64_t)s.info()->ctr[CTR_CLOSED] : s.closed_n, added_total, tot);
   return KHIP_OK;

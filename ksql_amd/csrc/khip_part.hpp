@@ -226,6 +226,9 @@ khip_status part_upload_plan(khip_agg* a, const std::vector<uint32_t>& image);
 khip_status part_plan_retry(khip_agg* a, RetryPlan& r, int pass, const std::vector<uint8_t>& host_fail);
 void part_retry_trace_counts(const RetryPlan& r, bool listed, const std::vector<uint8_t>& host_fail, int64_t* nsub,
                              int64_t* fail_table, int64_t* fail_region);
+khip_status part_pass_commit(khip_agg* a, int pass, const RetryPlan& r, const int64_t* gate, const uint32_t* prn,
+                             const unsigned long long* closed_ctr, int64_t nT);
+khip_status part_pass_failed(khip_agg* a, std::vector<uint8_t>* host_fail);
 void part_push_epilogue(khip_agg* a, int64_t closed_now, int64_t added, int64_t* tot);
 // khip_agg_c1.hip: the windowed COUNT(*) pipeline (declined = the general path must run)
 bool c1_eligible(khip_agg* a, int64_t n);

@@ -373,9 +373,13 @@ __global__ __launch_bounds__(T) void k_rs_pass(const uint64_t* __restrict__ kin,
   }
 }
 
-// Stable sort of (key, value) pairs by key bits [0, end_bit) (n < 2^32).  The sorted pairs end
-// in (k_out, v_out); k_in / v_in are clobbered.  tmp: histograms and tile status; alt: a third
-// key / value buffer, used when the pass count is even.
+// The sort's host side for one tile shape (T threads x IPT pairs per tile): `passes` LSD passes
+// (1..8) over the digits of key bits [0, 8 * passes), 1 <= n < 2^32.  Zeroes tmp — laid out as
+// [every pass's histogram | one ticket per pass | passes x tiles x 256 status words] — and launches
+// k_rs_ghist once and k_rs_pass per pass.  The passes ping-pong between the buffers so the last one
+// writes (k_out, v_out): an odd count alternates (k_in, v_in) and (k_out, v_out) and leaves alt
+// alone; an even count sends the first pass to alt (ensured here, n keys then n values).
+// k_in / v_in are clobbered when passes > 2.
 template <int T, int IPT, class V>
 khip_status sort_run(hipStream_t st, DevBuf& tmp, DevBuf& alt, uint64_t* k_in, uint64_t* k_out, V* v_in, V* v_out,
                      int64_t n, int passes) {
@@ -430,7 +434,9 @@ khip_status sort_run(hipStream_t st, DevBuf& tmp, DevBuf& alt, uint64_t* k_in, u
 
 // Stable sort of (key, value) pairs by key bits [0, end_bit) (n < 2^32).  The sorted pairs end
 // in (k_out, v_out); k_in / v_in are clobbered.  tmp: histograms and tile status; alt: a third
-// key / value buffer, used when the pass count is even.
+// key / value buffer, used when the pass count is even.  The pass count is ceil(end_bit / 8)
+// in 1..8, so whole digits are sorted, up to bit 8 * passes: callers keep their keys below
+// 2^end_bit.  n <= 0 is a no-op.
 template <class V>
 khip_status sort_pairs(hipStream_t st, DevBuf& tmp, DevBuf& alt, uint64_t* k_in, uint64_t* k_out, V* v_in, V* v_out,
                        int64_t n, int end_bit) {

@@ -284,6 +284,82 @@ def test_sessions_key_range_edges(prod, orc):
     o.close()
 
 
+# Key ranges for the engines' sort (SESSION: record keys; table sources: PRIMARY KEYs), as
+# (id, smallest key, range = largest - smallest, end_bit the sort runs over).  Dropped rows sort
+# under the sentinel key range + 1, so the sort covers the bits of range + 1: with a range of
+# 2^k - 1 the sentinel carries into a new bit, and at k = 8, 16, 32 into a new pass.  The full
+# 64-bit range has no sentinel.
+I64_MIN = -2 ** 63
+SORT_KEY_RANGES = [
+    ("bits33", -1000, 2 ** 32 + 12345, 33),
+    ("bits48", 7, 2 ** 47 + 3, 48),
+    ("bits56", -2 ** 40, 2 ** 55 + 9, 56),
+    ("bits64", -2 ** 62, 2 ** 63 + 5, 64),
+    ("full", I64_MIN, 2 ** 64 - 1, 64),
+    ("carry8", 100, 2 ** 8 - 1, 9),
+    ("carry16", -40_000, 2 ** 16 - 1, 17),
+    ("carry32", 5, 2 ** 32 - 1, 33),
+]
+SORT_PUSH_ROWS = (3 * 8192 + 1, 5000)  # four sort tiles (the last holds one pair), then one
+
+
+def sort_range_keys(rng, kmin, krange, end_bit, rows=SORT_PUSH_ROWS, distinct=9):
+    """Per push: keys on a few distinct values of [kmin, kmin + krange] with both ends present (rows
+    0 and 1), many rows per key; a mask of rows the caller must drop (NULL key or negative ts),
+    which leaves rows 0 and 1 alone."""
+    sentinel = krange + 1 if krange != 2 ** 64 - 1 else krange
+    assert sentinel.bit_length() == end_bit  # what sess_push / tagg_push derive from the range
+    offs = [0, krange] + [int(x) % (krange + 1) for x in rng.integers(0, 2 ** 63, distinct - 2)]
+    out = []
+    for n in rows:
+        pick = rng.integers(0, distinct, n)
+        pick[:2] = (0, 1)
+        keys = np.array([kmin + offs[j] for j in pick], np.int64)
+        drop = rng.random(n) < 0.04
+        drop[:2] = False
+        assert drop.any() and keys.min() == kmin and int(keys.max()) - kmin == krange
+        out.append((keys, drop))
+    return out
+
+
+@pytest.mark.parametrize("count_only", [True, False])
+@pytest.mark.parametrize("case", SORT_KEY_RANGES, ids=[c[0] for c in SORT_KEY_RANGES])
+def test_sessions_sort_key_ranges(prod, orc, case, count_only):
+    """The session sort at 5 to 8 passes on several tiles, and at the sentinel's carry into a new
+    bit / pass, with dropped rows in the push: nine keys with thousands of out-of-order records
+    each, so merges, late drops and the emitted changes depend on the arrival order the sort must
+    keep within a key.  Count-only handles sort the packed 8-byte records themselves; with argument
+    columns the sort carries 4-byte row indices and a gather follows."""
+    _, kmin, krange, end_bit = case
+    rng = np.random.default_rng(7000 + end_bit + (100 if count_only else 0) + krange % 97)
+    aggs = [("COUNT_STAR", -1)] if count_only else ALL_AGGS
+    kw = dict(window_kind="SESSION", size_ms=5_000, grace_ms=10_000, key_type="INT64",
+              col_types=[] if count_only else COLS, aggs=aggs)
+    g = abi.AggHandle(prod, abi.make_agg_desc(**dict(kw, flags=abi.FLAG_CHANGELOG)))
+    o = abi.AggHandle(orc, abi.make_agg_desc(**kw))
+    t0, emitted = 0, 0
+    for keys, drop in sort_range_keys(rng, kmin, krange, end_bit):
+        m = len(keys)
+        span = m * 500  # ~9 keys: a record per key every ~4.5 s against the 5 s gap
+        ts = t0 + np.sort(rng.integers(0, span, m)) + rng.integers(0, 20_000, m)
+        null_key = drop & (rng.random(m) < 0.5)
+        ts = np.where(drop & ~null_key, -1 - rng.integers(0, 50, m), ts)
+        cols = [] if count_only else [rng.integers(-9, 9, m).astype(np.int32), rng.integers(-9, 9, m),
+                                        rng.random(m), rng.random(m)]
+        b = abi.HostBatch(ts, keys=keys, key_valid=~null_key, cols=cols)
+        gs, os_ = g.push(b), o.push(b)
+        assert gs == os_
+        assert os_["dropped_null_key"] > 0 and os_["dropped_bad_ts"] > 0
+        gc, oc = g.changes(), o.changes()
+        _assert_changes_equal(gc, oc, g.desc)
+        emitted += gc["n"]
+        assert_snap_equal(g.snapshot(), o.snapshot(), g.desc, ABS_SUM, CNT_DBL)
+        t0 += span * 3 // 4
+    assert emitted > 1000  # hundreds of sessions per key
+    g.close()
+    o.close()
+
+
 @pytest.mark.parametrize("count_only", [True, False])
 def test_sessions_time_span_edges(prod, orc, count_only):
     """Replay records are packed to 8 bytes relative to the push's time base (smallest accepted ts,

@@ -17,6 +17,7 @@ import pytest
 
 import qtt
 from ksql_amd import abi
+from test_gpu_emit import SORT_KEY_RANGES, sort_range_keys
 
 CASES = qtt.load_cases("tagg")
 
@@ -171,6 +172,32 @@ def test_tagg_key_range_edges(prod, orc):
         for f in ("rows_in", "rows_accepted", "dropped_null_key", "dropped_bad_ts", "windows_applied", "stream_time"):
             assert a[f] == b[f], f
     _assert_same(g, o, 100.0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", SORT_KEY_RANGES, ids=[c[0] for c in SORT_KEY_RANGES])
+def test_tagg_sort_key_ranges(prod, orc, case):
+    """The PRIMARY KEY sort at 5 to 8 passes on several tiles, and at the sentinel's carry into a
+    new bit / pass, with dropped rows (NULL PRIMARY KEY, negative timestamp) in the push: nine
+    PRIMARY KEYs updated thousands of times each, moving between groups, so every key's final row
+    and the groups' undo / add sequence depend on the arrival order the sort must keep within a
+    key."""
+    _, kmin, krange, end_bit = case
+    rng = np.random.default_rng(8000 + end_bit + krange % 97)
+    batches = []
+    for pk, drop in sort_range_keys(rng, kmin, krange, end_bit):
+        b, sa, x = _changelog(rng, len(pk), 1, 20, False, False)
+        null_pk = drop & (rng.random(len(pk)) < 0.5)
+        b.ts[:] = np.where(drop & ~null_pk, -1, np.where(drop, b.ts, np.abs(b.ts)))
+        batches.append((b, {"src_keys": pk, "src_key_valid": ~null_pk}, x))
+    scale = sum(float(x.sum()) for _, _, x in batches) * 4
+    (g, gs), (o, os_) = (_run(lib, batches, False) for lib in (prod, orc))
+    for a, b in zip(gs, os_):
+        assert b["dropped_null_key"] > 0 and b["dropped_bad_ts"] > 0
+        for f in ("rows_in", "rows_accepted", "dropped_null_key", "dropped_bad_ts", "windows_applied", "stream_time"):
+            assert a[f] == b[f], f
+    assert o["n"] > 0
+    _assert_same(g, o, scale)
 
 
 @pytest.mark.gpu

@@ -138,6 +138,35 @@ typedef int32_t khip_status;
 #define KHIP_AGG_TOPK 8
 #define KHIP_AGG_TOPKDISTINCT 9
 #define KHIP_AGG_K(k) ((int32_t)(k) << 16)
+/* STDDEV_SAMP(col) / STDDEV_SAMPLE(col), col INTEGER / BIGINT:
+ * function/udaf/stddev/StandardDeviationSampUdaf.java:124-144 (aggregate), :170-176 (map),
+ * :179-196 (undo); StandardDeviationSampleUdaf.java:124-144, :168-174, :179-196.  NULL arguments are
+ * skipped.  The result is a DOUBLE, never SQL NULL: 0.0 for a group with fewer than two non-null
+ * records.  STDDEV_SAMP returns M2 / (count - 1), the sample VARIANCE, as the reference's map does
+ * (its QTT file: "has a bug and returns the square"); STDDEV_SAMPLE returns its square root.
+ *
+ * The reference folds a group's records in arrival order (Youngs-Cramer) in double arithmetic;
+ * here a group keeps exact integer state (count, Σx, Σx² over 64-bit words that only ever take
+ * commutative adds) and the result is decoded from it with one rounding:
+ *   M2 = RN((n Σx² - (Σx)²) / n),  STDDEV_SAMP = M2 / (double)(n - 1),  STDDEV_SAMPLE = sqrt of it.
+ * It is the value the reference's fold approximates, within (n + 8) * 2^-53 relative, and does not
+ * depend on record order, engine, retries or how the stream is cut into pushes.  The state is
+ * exact for up to 2^32 - 1 non-null records per group; beyond that the result is unspecified
+ * (nothing faults).  Deliberate divergence: where the reference's own Java arithmetic wraps (an
+ * INT sum past 2^31, x * (count + 1) past 2^63) its result is meaningless; here the result stays
+ * the true variance.
+ * A TableUdaf: allowed with KHIP_FLAG_TABLE_SOURCE (undo = word-wise subtraction), with every
+ * window kind but SESSION, both engines, every time domain, EMIT CHANGES / FINAL, and through
+ * khip_agg_push_shuffled.  State words: 2 (INT) or 5 (BIGINT) beyond the column's count and sum
+ * words, which COUNT / SUM / AVG of the same column share; both kinds of one column share all.
+ * KHIP_E_INVALID: KHIP_AGG_KEEP_NULLS or KHIP_AGG_K bits on these kinds.
+ * KHIP_E_UNSUPPORTED: a DOUBLE argument (no order-free state reproduces the fold within a bound
+ * that does not depend on the data's mean and spread), SESSION windows (the reference's session
+ * merge divides the integer sums with integer division, mergeInner :68-71: its merged sessions are
+ * not the variance of the union), a HAVING on the STDDEV aggregate itself (in the descriptor or
+ * passed to snapshot / get / count_rows), and an aggregate list past the 29 state words of a row. */
+#define KHIP_AGG_STDDEV_SAMP 10
+#define KHIP_AGG_STDDEV_SAMPLE 11
 
 /* Where a batch's column pointers live. */
 #define KHIP_MEM_HOST 0

@@ -31,7 +31,7 @@ AGG_KEEP_NULLS = 0x100  # KHIP_AGG_KEEP_NULLS: ignoreNulls = false, OR-ed into t
 AGG = {"COUNT_STAR": 0, "COUNT": 1, "SUM": 2, "MIN": 3, "MAX": 4, "AVG": 5,
        "LATEST_BY_OFFSET": 6, "EARLIEST_BY_OFFSET": 7,
        "LATEST_BY_OFFSET_NULLS": 6 | AGG_KEEP_NULLS, "EARLIEST_BY_OFFSET_NULLS": 7 | AGG_KEEP_NULLS,
-       "TOPK": 8, "TOPKDISTINCT": 9}
+       "TOPK": 8, "TOPKDISTINCT": 9, "STDDEV_SAMP": 10, "STDDEV_SAMPLE": 11}
 
 
 def AGG_K(k):
@@ -442,7 +442,7 @@ def result_types(desc):
         k = desc.aggs[i].kind
         if k in (AGG["COUNT_STAR"], AGG["COUNT"]):
             out.append(TYPE["INT64"])
-        elif k == AGG["AVG"]:
+        elif k in (AGG["AVG"], AGG["STDDEV_SAMP"], AGG["STDDEV_SAMPLE"]):
             out.append(TYPE["DOUBLE"])
         else:  # SUM / MIN / MAX, LATEST / EARLIEST_BY_OFFSET (scalar and N forms, with or without AGG_KEEP_NULLS),
             # TOPK / TOPKDISTINCT

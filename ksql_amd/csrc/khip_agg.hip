@@ -34,6 +34,7 @@
 #include "khip_util.hpp"
 
 #include "khip_agg_internal.hpp"
+#include "khip_variance.hpp"
 
 namespace khip {
 
@@ -241,7 +242,11 @@ __device__ __forceinline__ int upsert_apply(const ApplyParams& p, uint64_t* __re
             }
             break;
           }
-          default:
+          default:  // OP_ADD_HI32 / OP_ADD_SQ (STDDEV: x >> 32 / a limb of x², khip_variance.hpp); here, so
+                    // that the dispatch of the kinds above stays what it was
+            if (op.kind == OP_ADD_HI32 || op.kind == OP_ADD_SQ)
+              __hip_atomic_fetch_add((uint64_t*)w, var_addend(op, load_col_raw(cols, ty, op.col, row)),
+                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             break;
         }
       }
@@ -1176,6 +1181,10 @@ static inline bool agg_is_topk(int32_t kind) {
   const int b = agg_base_kind(kind);
   return b == KHIP_AGG_TOPK || b == KHIP_AGG_TOPKDISTINCT;
 }
+static inline bool agg_is_var(int32_t kind) {
+  const int b = agg_base_kind(kind);
+  return b == KHIP_AGG_STDDEV_SAMP || b == KHIP_AGG_STDDEV_SAMPLE;
+}
 static inline bool off_has_lists(const OffResolve& q) {
   for (int k = 0; k < q.n; k++)
     if (q.a[k].n) return true;
@@ -1235,7 +1244,7 @@ static khip_status plan_state(khip_agg* a) {
     a->offs.a[a->offs.n++] = o;
   }
   const int nc = d.n_cols + a->n_hidden;  // internal argument columns
-  std::vector<int> w_cnt(nc, -1), w_sum(nc, -1), w_min(nc, -1), w_max(nc, -1);
+  std::vector<int> w_cnt(nc, -1), w_sum(nc, -1), w_min(nc, -1), w_max(nc, -1), w_hi(nc, -1), w_sq(nc, -1);
   for (int i = 0; i < d.n_aggs; i++) {
     const khip_agg_spec& s = a->aggs[i];
     if (agg_is_offset(s.kind)) continue;
@@ -1251,7 +1260,15 @@ static khip_status plan_state(khip_agg* a) {
     // the column's non-null count: COUNT(col), AVG's divisor, MIN/MAX's null test.  SUM alone needs
     // none (SUM over only NULLs is 0, SumKudaf's initial value): its rows stay 32 bytes
     if (s.kind != KHIP_AGG_SUM && w_cnt[c] < 0) w_cnt[c] = word++;
-    if ((s.kind == KHIP_AGG_SUM || s.kind == KHIP_AGG_AVG) && w_sum[c] < 0) w_sum[c] = word++;
+    if ((s.kind == KHIP_AGG_SUM || s.kind == KHIP_AGG_AVG || agg_is_var(s.kind)) && w_sum[c] < 0) w_sum[c] = word++;
+    // STDDEV_SAMP / STDDEV_SAMPLE (khip_variance.hpp): beside the count and the sum, Σ (x >> 32) for
+    // a BIGINT and the 32-bit limbs of Σx², one word each; both kinds of a column share them
+    if (agg_is_var(s.kind) && w_sq[c] < 0) {
+      const bool big = a->col_types[c] == KHIP_TYPE_INT64;
+      if (big) w_hi[c] = word++;
+      w_sq[c] = word;
+      word += big ? 4 : 2;
+    }
     if (s.kind == KHIP_AGG_MIN && w_min[c] < 0) w_min[c] = word++;
     if (s.kind == KHIP_AGG_MAX && w_max[c] < 0) w_max[c] = word++;
   }
@@ -1328,6 +1345,9 @@ static khip_status plan_state(khip_agg* a) {
   for (int c = 0; c < nc; c++) {
     if (w_cnt[c] >= 0) add(OP_INC_VALID, c, w_cnt[c]);
     if (w_sum[c] >= 0) add(p.col_type[c] == KHIP_TYPE_DOUBLE ? OP_ADD_F64 : OP_ADD_I64, c, w_sum[c]);
+    if (w_hi[c] >= 0) add(OP_ADD_HI32, c, w_hi[c]);
+    if (w_sq[c] >= 0)  // (op_word / op_slots: the limb index)
+      for (int j = 0; j < (p.col_type[c] == KHIP_TYPE_INT64 ? 4 : 2); j++) add(OP_ADD_SQ, c, (w_sq[c] + j) | (j << 8));
     if (w_min[c] >= 0) add(OP_MIN, c, w_min[c]);
     if (w_max[c] >= 0) add(OP_MAX, c, w_max[c]);
   }
@@ -1344,6 +1364,8 @@ static khip_status plan_state(khip_agg* a) {
   for (const TopkSpan& sp : spans)  // (the flag word stays 0)
     for (int j = 0; j < sp.k; j++) a->init.w[sp.word + j] = INT64_MIN;
   a->outs.clear();
+  a->out_var.assign(d.n_aggs, khip_agg::VarWords{});
+  a->has_var = false;
   for (int i = 0; i < d.n_aggs; i++) {
     const khip_agg_spec& s = a->aggs[i];
     AggOut o{};
@@ -1355,6 +1377,13 @@ static khip_status plan_state(khip_agg* a) {
       case KHIP_AGG_COUNT: o.w_val = w_cnt[s.arg_col]; break;
       case KHIP_AGG_SUM:
       case KHIP_AGG_AVG: o.w_val = w_sum[s.arg_col]; break;
+      case KHIP_AGG_STDDEV_SAMP:
+      case KHIP_AGG_STDDEV_SAMPLE:  // (decoded by emit_snapshot: variance_result)
+        o.w_val = w_sum[s.arg_col];
+        a->out_var[i].w_hi = w_hi[s.arg_col];
+        a->out_var[i].w_sq = w_sq[s.arg_col];
+        a->has_var = true;
+        break;
       case KHIP_AGG_MIN: o.w_val = w_min[s.arg_col]; break;
       case KHIP_AGG_MAX: o.w_val = w_max[s.arg_col]; break;
       case KHIP_AGG_LATEST_BY_OFFSET:
@@ -1502,7 +1531,7 @@ khip_status khip_agg_result_type(const khip_agg_desc* d, int32_t i, int32_t* out
   if (!d || !out || i < 0 || i >= d->n_aggs) return fail(KHIP_E_INVALID, "bad aggregate index");
   const khip_agg_spec& s = d->aggs[i];
   if (s.kind == KHIP_AGG_COUNT_STAR || s.kind == KHIP_AGG_COUNT) *out = KHIP_TYPE_INT64;
-  else if (s.kind == KHIP_AGG_AVG) *out = KHIP_TYPE_DOUBLE;
+  else if (s.kind == KHIP_AGG_AVG || agg_is_var(s.kind)) *out = KHIP_TYPE_DOUBLE;
   else *out = d->col_types[s.arg_col];  // (TOPK / TOPKDISTINCT: the element type)
   return KHIP_OK;
 }
@@ -1536,7 +1565,7 @@ khip_status khip_agg_create(const khip_agg_desc* desc, khip_agg** out) {
   for (int i = 0; i < d.n_aggs; i++) {
     const khip_agg_spec& s = d.aggs[i];
     const int bk = agg_base_kind(s.kind);
-    if (bk < KHIP_AGG_COUNT_STAR || bk > KHIP_AGG_TOPKDISTINCT) return fail(KHIP_E_INVALID, "aggregate kind");
+    if (bk < KHIP_AGG_COUNT_STAR || bk > KHIP_AGG_STDDEV_SAMPLE) return fail(KHIP_E_INVALID, "aggregate kind");
     if ((s.kind & KHIP_AGG_KEEP_NULLS) && !agg_is_offset(s.kind))
       return fail(KHIP_E_INVALID, "KHIP_AGG_KEEP_NULLS on an aggregate other than LATEST / EARLIEST_BY_OFFSET");
     if (agg_is_offset(s.kind)) {  // no k bits: the scalar form; N >= 1: the N form (an ARRAY, also for N = 1)
@@ -1550,6 +1579,18 @@ khip_status khip_agg_create(const khip_agg_desc* desc, khip_agg** out) {
       return fail(KHIP_E_INVALID, "aggregate argument column");
     has_offset = has_offset || agg_is_offset(s.kind);
     has_topk = has_topk || agg_is_topk(s.kind);
+    if (agg_is_var(s.kind)) {
+      // a DOUBLE argument: no order-free state reproduces the reference's fold within a bound that
+      // does not depend on the data's mean and spread
+      if (d.col_types[s.arg_col] == KHIP_TYPE_DOUBLE)
+        return fail(KHIP_E_UNSUPPORTED, "STDDEV_SAMP / STDDEV_SAMPLE of a DOUBLE column");
+      // the reference's session merge divides the integer sums with integer division
+      // (StandardDeviationSampUdaf.java:68-71): its merged sessions are not the variance of the union
+      if (d.window_kind == KHIP_WINDOW_SESSION)
+        return fail(KHIP_E_UNSUPPORTED, "STDDEV_SAMP / STDDEV_SAMPLE with SESSION windows");
+      if (d.has_having && d.having.agg_index == i)
+        return fail(KHIP_E_UNSUPPORTED, "HAVING on a STDDEV_SAMP / STDDEV_SAMPLE aggregate");
+    }
   }
   if (has_topk) {
     // merged list by list (TopkKudaf.merge) in the reference: not on the device
@@ -2353,6 +2394,8 @@ static khip_status compact_rows(khip_agg* a, const khip_having* h, std::vector<u
       return fail(KHIP_E_UNSUPPORTED, "HAVING on a LATEST / EARLIEST_BY_OFFSET aggregate");
     if (agg_is_topk(a->aggs[h->agg_index].kind))  // (nor the TOPK kinds: an ARRAY has no comparison)
       return fail(KHIP_E_UNSUPPORTED, "HAVING on a TOPK / TOPKDISTINCT aggregate (an ARRAY)");
+    if (agg_is_var(a->aggs[h->agg_index].kind))  // (nor the STDDEV kinds: decoded on the host from several words)
+      return fail(KHIP_E_UNSUPPORTED, "HAVING on a STDDEV_SAMP / STDDEV_SAMPLE aggregate");
     hd.active = 1;
     hd.op = h->op;
     hd.a = a->outs[h->agg_index];
@@ -2584,6 +2627,14 @@ static khip_status emit_snapshot(khip_agg* a, const std::vector<uint64_t>& rows,
           if ((int64_t)s[f.w_seq] == none || (f.w_null >= 0 && s[f.w_null] != 0)) isnull = true;
           else if (o.type == KHIP_TYPE_DOUBLE) memcpy(&dv, &s[f.w_val], 8);  // the bits: NaN payloads, -0.0
           else iv = (int64_t)s[f.w_val];
+          break;
+        }
+        case KHIP_AGG_STDDEV_SAMP:
+        case KHIP_AGG_STDDEV_SAMPLE: {  // never NULL: 0.0 below two records (map :171-174)
+          const khip_agg::VarWords& v = a->out_var[i];
+          const bool big = o.type == KHIP_TYPE_INT64;
+          dv = variance_result(o.kind == KHIP_AGG_STDDEV_SAMPLE, big, (int64_t)s[o.w_cnt], s[o.w_val],
+                               big ? s[v.w_hi] : 0, &s[v.w_sq], big ? 4 : 2);
           break;
         }
         case KHIP_AGG_AVG: {

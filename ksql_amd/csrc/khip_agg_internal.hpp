@@ -24,17 +24,34 @@ enum { P_ACCEPTED, P_NULL_KEY, P_NULL_ROW, P_BAD_TS, P_APPLIED, P_LATE, P_FAILED
 // consecutive state words from op_word(op) hold order keys sorted descending, INT64_MIN = empty;
 // a record's key is inserted by the chain in lds_apply / upsert_apply.  Only k_part_agg and k_apply
 // know the two kinds: a handle with one takes no other aggregate kernel.
-enum OpKind : int8_t { OP_INC = 0, OP_INC_VALID, OP_ADD_I64, OP_ADD_F64, OP_MIN, OP_MAX, OP_TOPK, OP_TOPK_DISTINCT };
+//
+// OP_ADD_HI32 / OP_ADD_SQ (STDDEV_SAMP / STDDEV_SAMPLE over INT / BIGINT, khip_variance.hpp): plain
+// u64 adds like OP_ADD_I64, of x >> 32 (arithmetic) and of the 32-bit limb op_slots(op) of x² (x
+// sign-extended, the square 128 bits wide): var_addend.  k_part_agg, k_apply and the table engine's
+// k_tagg_apply know them; a handle with one takes no other aggregate kernel (khip_agg::has_var).
+enum OpKind : int8_t {
+  OP_INC = 0, OP_INC_VALID, OP_ADD_I64, OP_ADD_F64, OP_MIN, OP_MAX, OP_TOPK, OP_TOPK_DISTINCT, OP_ADD_HI32, OP_ADD_SQ
+};
 
 struct UpdOp {
   int8_t kind;
   int8_t col;
-  int16_t word;  // the state word; the TOPK kinds: first slot word | slots << 8 (state words are < 32)
+  int16_t word;  // the state word; the TOPK kinds: first slot word | slots << 8 (state words are < 32);
+                 // OP_ADD_SQ: the word | limb index << 8
 };
 // (the slot count shares `word` so that the struct, and with it the parameter blocks and the code of
 // every kernel that never sees a TOPK op, stay what they were)
 __host__ __device__ __forceinline__ int op_word(const UpdOp& o) { return o.word & 0xFF; }
 __host__ __device__ __forceinline__ int op_slots(const UpdOp& o) { return (o.word >> 8) & 0xFF; }
+
+// What OP_ADD_HI32 / OP_ADD_SQ add to their word for the argument x (INT: sign-extended).
+__device__ __forceinline__ uint64_t var_addend(const UpdOp& o, int64_t x) {
+  if (o.kind == OP_ADD_HI32) return (uint64_t)(x >> 32);
+  const uint64_t m = x < 0 ? 0 - (uint64_t)x : (uint64_t)x;  // (Long.MIN_VALUE: 2^63)
+  const int j = op_slots(o);
+  const uint64_t half = j < 2 ? m * m : __umul64hi(m, m);
+  return (j & 1) ? half >> 32 : half & 0xFFFFFFFFull;
+}
 
 struct ApplyParams {
   int32_t windowed;
@@ -732,6 +749,14 @@ struct khip_agg {
   // the N forms as well, whose slots are OP_TOPK ops.
   std::vector<int> agg_k, out_flag;
   bool has_topk = false;
+  // ---- STDDEV_SAMP / STDDEV_SAMPLE: out_var[i] = the aggregate's column state beyond the count
+  // (AggOut::w_cnt) and sum (w_val) words — the x >> 32 word (BIGINT; -1: INT) and the first of the
+  // 2 (INT) / 4 (BIGINT) consecutive limb words of Σx²; w_sq < 0: not a STDDEV aggregate.
+  // has_var: the handle has OP_ADD_HI32 / OP_ADD_SQ ops, which only k_part_agg / k_apply /
+  // k_tagg_apply know (part_push: merge_allow; the c1 / c1v pipelines decline any op past OP_MAX).
+  struct VarWords { int w_hi = -1, w_sq = -1; };
+  std::vector<VarWords> out_var;
+  bool has_var = false;
   int sw = 4;
   // table
   DevBuf table;

@@ -1445,7 +1445,11 @@ __device__ __forceinline__ void lds_apply(const PartAggParams& q, lds_i64* lw, i
         }
         break;
       }
-      default: break;
+      default:  // OP_ADD_HI32 / OP_ADD_SQ (STDDEV: x >> 32 / a limb of x², khip_variance.hpp; ds_add_u64);
+                // here, so that the dispatch of the kinds above stays what it was
+        if (op.kind == OP_ADD_HI32 || op.kind == OP_ADD_SQ)
+          __hip_atomic_fetch_add((KLDS uint64_t*)w, var_addend(op, raw), WG_RLX);
+        break;
     }
   }
 }
@@ -3953,8 +3957,9 @@ static PartGeo part_plan(const khip_agg* a, int64_t n) {
   g.q0 = part_params(a);
   g.close0 = (a->windowed && a->host_stream_time >= 0) ? a->host_stream_time - a->grace : INT64_MIN;
   // which aggregate kernel pass 0 runs, as far as the host knows (k_part_wrange has the last word)
-  // (a TOPK / TOPKDISTINCT handle: k_part_agg only — the merges have no plane form of the chain)
-  g.merge_allow = s.mH >= 256 && knob("KHIP_MERGE", 1) != 0 && !a->has_topk;
+  // (a TOPK / TOPKDISTINCT handle: k_part_agg only — the merges have no plane form of the chain;
+  // a STDDEV handle too: the merges do not know its ops)
+  g.merge_allow = s.mH >= 256 && knob("KHIP_MERGE", 1) != 0 && !a->has_topk && !a->has_var;
   const int64_t r12_mode = knob("KHIP_R12", 1);  // 1: 12-byte records end to end; 2: pass A only
   g.r12_ok = g.narrow && !g.pad && g.merge_allow && r12_mode != 0;
   g.r12_merge = g.r12_ok && (r12_mode == 1 || !g.lvl2);  // what k_part_merge reads

@@ -292,7 +292,10 @@ __device__ __forceinline__ uint64_t op_delta(const UpdOp op, bool has_add, const
       const double y = vs ? __longlong_as_double(wpick(sub, op.col)) : 0.0;
       return (uint64_t)__double_as_longlong(va && vs ? x - y : (va ? x : -y));
     }
-    default:  // MIN / MAX are rejected at create (not undoable)
+    default:  // MIN / MAX are rejected at create (not undoable); STDDEV's OP_ADD_HI32 / OP_ADD_SQ
+              // (khip_variance.hpp): undo = the word-wise difference, mod 2^64
+      if (op.kind == OP_ADD_HI32 || op.kind == OP_ADD_SQ)
+        return (va ? var_addend(op, wpick(add, op.col)) : 0) - (vs ? var_addend(op, wpick(sub, op.col)) : 0);
       return 0;
   }
 }
@@ -449,7 +452,7 @@ __global__ __launch_bounds__(256) void k_tagg_apply(TaggArgs A, const uint64_t* 
         __hip_atomic_fetch_max((int64_t*)&gsl[2], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       for (int q = 0; q < A.p.n_ops; q++) {
         const UpdOp op = A.p.ops[q];
-        op_add_atomic(op, &gsl[op.word], op_delta<NC>(op, has_add, add, has_sub, sub));
+        op_add_atomic(op, &gsl[op_word(op)], op_delta<NC>(op, has_add, add, has_sub, sub));
       }
     };
     // Replay the key's changes in arrival order.  Every change undoes the previous row from its

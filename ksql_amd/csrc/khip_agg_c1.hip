@@ -24,7 +24,10 @@
 //                 inside the bucket (LDS), written bucket-contiguously; the chunk's per-partition
 //                 offsets (u16) go to a segment table
 //   k_c1_merge    persistent workgroups, one partition per item: the partition's records are its
-//                 segments of the bucket's chunks; (key - kmin, window) → a 32-bit identity when
+//                 segments of the bucket's chunks (an LDS table of prefix | (base - prefix) << 32
+//                 per segment, the base relative to the bucket's first record: a lane looks its
+//                 AU records up together, c1_seg_lookup, and loads them from the bucket's uniform
+//                 base + a 32-bit offset); (key - kmin, window) → a 32-bit identity when
 //                 it fits (no key hash on the record path), LDS identity CAS + u32 row-time max +
 //                 u32 count, claimed entries listed (the write-out walks the list, not the table);
 //                 resident rows merged, closed rows evicted, HAVING counts and changelog flags
@@ -802,9 +805,81 @@ __device__ __forceinline__ unsigned long long c1_reserve_closed(unsigned long lo
   return C1_NOSLOT;
 }
 
+// Segment lookup of a lane's AU records at once: record li = min(l0 + thread + u NT, rn - 1) of
+// the item whose segment table is in LDS lies at at[u] = base(segment) + li, in 32-bit arithmetic
+// (an item has fewer than 2^31 records, a bucket at most C1_SEGMAX x C1_CH).  An entry is
+// prefix | (base - prefix) << 32 and sg2[nseg] holds the total, so a record's segment is the last
+// one whose prefix is <= li.  Staged, so the LDS round trips of the AU records overlap: every
+// block → segment read then one wait, every entry pair then one wait, then ONE loop in which all
+// still-unresolved records step on together (uniform exit through a ballot, every read
+// unconditional).  Items past C1_SEGOF << segb records search the prefixes instead, the AU
+// searches in step.  rn, nseg and segb are wave-uniform; rn >= 1.
+typedef uint64_t c1_sgpair __attribute__((ext_vector_type(2), aligned(8)));  // two neighbouring entries
+template <int AU, int NT>
+__device__ __forceinline__ void c1_seg_lookup(const KLDS uint64_t* sg2, const KLDS uint16_t* segof, uint32_t l0,
+                                              uint32_t rn, int nseg, int segb, uint32_t (&at)[AU]) {
+  uint32_t li[AU];
+#pragma unroll
+  for (int u = 0; u < AU; u++) {
+    const uint32_t i = l0 + threadIdx.x + (uint32_t)(u * NT);
+    li[u] = i < rn ? i : rn - 1u;
+  }
+  if (rn <= ((uint32_t)C1_SEGOF << segb)) {  // from the block's segment, a step or two on
+    int lo[AU];
+    uint32_t ba[AU];  // base - prefix of segment lo
+    uint64_t sb[AU];  // entry lo + 1
+#pragma unroll
+    for (int u = 0; u < AU; u++) lo[u] = (int)segof[li[u] >> segb];
+#pragma unroll
+    for (int u = 0; u < AU; u++) {  // entries lo and lo + 1 in one read (ds_read2_b64)
+      const c1_sgpair pr = *(const KLDS c1_sgpair*)(sg2 + lo[u]);
+      ba[u] = (uint32_t)(pr.x >> 32);
+      sb[u] = pr.y;
+    }
+    for (;;) {  // (sg2[nseg] = the total > li: no step leaves the table)
+      bool any = false;
+#pragma unroll
+      for (int u = 0; u < AU; u++) any |= (uint32_t)sb[u] <= li[u];
+      if (!__ballot(any)) break;
+      for (int u = 0; u < AU; u++) {  // (unrolled with the loop above; a pragma here only warns)
+        const bool on = (uint32_t)sb[u] <= li[u];
+        lo[u] += on ? 1 : 0;
+        ba[u] = on ? (uint32_t)(sb[u] >> 32) : ba[u];
+        sb[u] = sg2[lo[u] + 1];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < AU; u++) at[u] = ba[u] + li[u];
+  } else {
+    // the last segment whose prefix is <= li: sg2[lo] <= li < sg2[hi] holds throughout (a search
+    // that has converged reads mid = lo and stays)
+    uint32_t lo[AU], hi[AU];
+#pragma unroll
+    for (int u = 0; u < AU; u++) {
+      lo[u] = 0u;
+      hi[u] = (uint32_t)nseg;
+    }
+    for (int span = nseg; span > 1; span = (span + 1) >> 1) {  // the widest interval left: uniform
+      uint32_t pm[AU];
+#pragma unroll
+      for (int u = 0; u < AU; u++) pm[u] = (uint32_t)sg2[(lo[u] + hi[u]) >> 1];
+#pragma unroll
+      for (int u = 0; u < AU; u++) {
+        const uint32_t mid = (lo[u] + hi[u]) >> 1;
+        const bool up = pm[u] <= li[u];
+        lo[u] = up ? mid : lo[u];
+        hi[u] = up ? hi[u] : mid;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < AU; u++) at[u] = (uint32_t)(sg2[lo[u]] >> 32) + li[u];
+  }
+}
+
 // Work item: p (work == nullptr: item w is partition w) or work[w] = p | sbits << 16 | sub << 20
 // (a retry with 2^sbits sub-passes).  LDS: ids ID[H + 64] | rt u32[H + 64] | ct u32[H + 64] |
-// list u16[H] | segment prefix u32[SEGMAX + 1] | segment bases i32[SEGMAX] (n < 2^31).
+// list u16[H] | segment entries u64[SEGMAX + 4] (prefix | (base in the bucket - prefix) << 32) |
+// bucket bases and chunk starts | block → segment u16[SEGOF].
 template <int NT, int AU, class ID, bool WIDE>
 __global__ __launch_bounds__(NT, 4) void k_c1_merge(
     C1Q q, const uint32_t* __restrict__ work, int64_t nwork, const int64_t* __restrict__ bb,
@@ -881,22 +956,36 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
     *h = c1_hash<ID>(*id);
     return true;
   };
-  // item w's descriptor, and its segments in LDS (prefix of their lengths, each one's base:
-  // record li = srec[sbs[s] + li]).  fetch issues the global loads only (the raw words stay in
-  // registers, nothing waits on them): it runs for item w + grid at the start of item w, so the
+  // item w's descriptor, and its segments in LDS (prefix of their lengths, each one's base in the
+  // bucket: record li = srec[bb0 + base(s) + li - prefix(s)]).  fetch issues the global loads
+  // only (the raw words stay in registers, nothing waits on them): it runs for item w + grid at
+  // the start of item w, so the
   // loads are in flight through w's records.  prep (the whole workgroup, barriers inside) turns
   // them into the LDS segment table once w's records are in the table.
   struct Pre {
     uint32_t p;
-    int sbits, sub, nseg;
-    int64_t nrow, bb0;
+    int sbits, sub;
+    int64_t nrow;
     uint32_t selw;
-    uint16_t s00, s01, s10, s11;  // seg[k0][f], seg[k0][f + 1], seg[k0 + 1][f], seg[k0 + 1][f + 1]
+    // seg[k0][f] | seg[k0][f + 1] << 16 and the same of k0 + 1 (the bucket's segment count and base
+    // are read again by prep: nothing of them is held through the item's records)
+    uint32_t s0, s1;
+  };
+  // the segments of partition p's bucket: their count, the first one's index, the bucket's base
+  auto bucket = [&](uint32_t p, int& cs, int64_t& bb0) -> int {
+    const int b = (int)(p >> q.fbits);
+    cs = lcs[b];
+    bb0 = lbb[b];
+    const int nseg = lcs[b + 1] - cs;
+    return nseg < 0 || nseg > C1_SEGMAX ? 0 : nseg;  // (k_c1_check guarantees 0 <= nseg <= SEGMAX)
   };
   struct It {
     uint32_t p;
     int sbits, sub, nseg, segb;  // segb: log2 of the records per segment-lookup block
-    int64_t rn, nrow;
+    uint32_t rn;                 // records (< 2^31)
+    uint32_t bb0;                // the bucket's first record in srec (k_c1_bases: a u32 scan's value);
+                                 // the segment bases are relative to it
+    int64_t nrow;
     bool isel;
   };
   auto fetch = [&](int64_t w, Pre& r) {
@@ -911,43 +1000,41 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
       p = (uint32_t)w;
     }
     p = __builtin_amdgcn_readfirstlane(p);
-    const int b = (int)(p >> q.fbits), f = (int)(p & (uint32_t)(F - 1));
-    const int cs = lcs[b];
-    int nseg = lcs[b + 1] - cs;
-    if (nseg < 0 || nseg > C1_SEGMAX) nseg = 0;  // (k_c1_check guarantees 0 <= nseg <= SEGMAX)
+    const int f = (int)(p & (uint32_t)(F - 1));
+    int cs;
+    int64_t bb0;
+    const int nseg = bucket(p, cs, bb0);
     r.p = p;
     r.sbits = sbits;
     r.sub = sub;
-    r.nseg = nseg;
     r.nrow = cnt[p];
     r.selw = ((const uint32_t*)sel)[p >> 2];
-    r.bb0 = lbb[b];
     const int k0 = threadIdx.x * 2;
-    r.s00 = r.s01 = r.s10 = r.s11 = 0;
+    r.s0 = r.s1 = 0u;
     if (k0 < nseg) {
       const uint16_t* sg = seg + (int64_t)(cs + k0) * (F + 1) + f;
-      r.s00 = sg[0];
-      r.s01 = sg[1];
+      r.s0 = (uint32_t)sg[0] | (uint32_t)sg[1] << 16;
     }
     if (k0 + 1 < nseg) {
       const uint16_t* sg = seg + (int64_t)(cs + k0 + 1) * (F + 1) + f;
-      r.s10 = sg[0];
-      r.s11 = sg[1];
+      r.s1 = (uint32_t)sg[0] | (uint32_t)sg[1] << 16;
     }
   };
   auto prep = [&](const Pre& r, It& it) {
-    const int nseg = r.nseg;
+    int cs;
+    int64_t bb0;
+    const int nseg = bucket(r.p, cs, bb0);
     it.p = r.p;
     it.sbits = r.sbits;
     it.sub = r.sub;
-    it.nseg = nseg;
     it.nrow = r.nrow;
     it.isel = ((r.selw >> (8 * (r.p & 3))) & 0xFFu) != 0;
     const int k0 = threadIdx.x * 2;
-    const int len0 = k0 < nseg ? (int)r.s01 - (int)r.s00 : 0;
-    const int len1 = k0 + 1 < nseg ? (int)r.s11 - (int)r.s10 : 0;
-    const int64_t base0 = r.bb0 + (int64_t)k0 * C1_CH + r.s00;
-    const int64_t base1 = r.bb0 + (int64_t)(k0 + 1) * C1_CH + r.s10;
+    const uint32_t s00 = r.s0 & 0xFFFFu, s10 = r.s1 & 0xFFFFu;
+    const int len0 = k0 < nseg ? (int)(r.s0 >> 16) - (int)s00 : 0;
+    const int len1 = k0 + 1 < nseg ? (int)(r.s1 >> 16) - (int)s10 : 0;
+    const uint32_t base0 = (uint32_t)(k0 * C1_CH) + s00;  // relative to the bucket's first record
+    const uint32_t base1 = (uint32_t)((k0 + 1) * C1_CH) + s10;
     const int s = len0 + len1;
     int incl = s;
     for (int off = 1; off < 64; off <<= 1) {
@@ -967,8 +1054,8 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
     // records on average: 32-record blocks make the lookup a read and at most a step or two)
     const int segb = tot <= (C1_SEGOF << 5) ? 5 : (tot <= (C1_SEGOF << 6) ? 6 : C1_SEGB);
     const int bm = (1 << segb) - 1;
-    if (k0 < nseg) sg2[k0] = (uint32_t)ex | (uint64_t)(uint32_t)(int32_t)(base0 - ex) << 32;
-    if (k0 + 1 < nseg) sg2[k0 + 1] = (uint32_t)(ex + len0) | (uint64_t)(uint32_t)(int32_t)(base1 - (ex + len0)) << 32;
+    if (k0 < nseg) sg2[k0] = (uint32_t)ex | (uint64_t)(base0 - (uint32_t)ex) << 32;
+    if (k0 + 1 < nseg) sg2[k0 + 1] = (uint32_t)(ex + len0) | (uint64_t)(base1 - (uint32_t)(ex + len0)) << 32;
     // segment lookup: block j (records [j << segb, (j + 1) << segb)) starts in segment segof[j]
     for (int bj = (ex + bm) >> segb, be = (ex + len0 + bm) >> segb; bj < be && bj < C1_SEGOF; bj++)
       segof[bj] = (uint16_t)k0;
@@ -977,47 +1064,35 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
     if (k0 < nseg && k0 + 2 >= nseg) sg2[nseg] = (uint32_t)(ex + s);  // the total
     if (nseg == 0 && threadIdx.x == 0) sg2[0] = 0u;
     lds_barrier();
-    it.rn = (uint32_t)sg2[nseg];
-    it.segb = segb;
+    // (the same in every lane: held in scalar registers, so the record loop's control flow is
+    // uniform and the bucket's base is a scalar address)
+    it.rn = __builtin_amdgcn_readfirstlane((uint32_t)sg2[nseg]);
+    it.segb = __builtin_amdgcn_readfirstlane(segb);
+    it.nseg = __builtin_amdgcn_readfirstlane(nseg);
+    it.bb0 = __builtin_amdgcn_readfirstlane((uint32_t)bb0);
   };
   uint64_t ra[AU], rb[AU];
   uint32_t ta[AU], tb[AU];  // WIDE: the records' ts words
   // records li = l0 + thread + u NT of the item whose segments are in LDS (indices clamped to the
-  // last record: every load is unconditional, so the waits stay counted)
-  auto load = [&](uint64_t (&x)[AU], uint32_t (&tx)[AU], int64_t l0, int64_t rn, int nseg, int segb) {
+  // last record: every load is unconditional, so the waits stay counted).  A record's address is
+  // the bucket's base (uniform) plus a 32-bit byte offset.
+  auto load = [&](uint64_t (&x)[AU], uint32_t (&tx)[AU], uint32_t l0, const It& t) {
+    uint32_t at[AU];
+    c1_seg_lookup<AU, NT>(sg2, segof, l0, t.rn, t.nseg, t.segb, at);
+    const char* sb = (const char*)(srec + t.bb0);
 #pragma unroll
-    for (int u = 0; u < AU; u++) {
-      int64_t li = l0 + threadIdx.x + (int64_t)u * NT;
-      li = li < rn ? li : rn - 1;
-      int lo = 0;  // the last segment starting at or before li
-      int64_t at;
-      if (rn <= ((int64_t)C1_SEGOF << segb)) {  // from the block's segment, a step or two on
-        lo = segof[li >> segb];
-        uint64_t sa = sg2[lo], sb = sg2[lo + 1];  // one ds_read2_b64
-        while (lo + 1 < nseg && (int64_t)(uint32_t)sb <= li) {
-          lo++;
-          sa = sb;
-          sb = sg2[lo + 1];
-        }
-        at = (int64_t)(int32_t)(sa >> 32) + li;
-      } else {
-        int hi = nseg;
-        while (hi - lo > 1) {
-          const int mid = (lo + hi) >> 1;
-          if ((int64_t)(uint32_t)sg2[mid] <= li) lo = mid;
-          else hi = mid;
-        }
-        at = (int64_t)(int32_t)(sg2[lo] >> 32) + li;
-      }
-      x[u] = c1_ld(srec + at);
-      if constexpr (WIDE) tx[u] = c1_ld(srecT + at);
+    for (int u = 0; u < AU; u++) x[u] = c1_ld((const uint64_t*)(sb + (uint64_t)(uint32_t)(at[u] << 3)));
+    if constexpr (WIDE) {
+      const char* sbT = (const char*)(srecT + t.bb0);
+#pragma unroll
+      for (int u = 0; u < AU; u++) tx[u] = c1_ld((const uint32_t*)(sbT + (uint64_t)(uint32_t)(at[u] << 2)));
     }
   };
   // the item's first two chunks (register sets A and B): a chunk is always two chunks ahead of
   // the one being applied
   auto load01 = [&](const It& x) {
-    if (x.rn > 0) load(ra, ta, 0, x.rn, x.nseg, x.segb);
-    if (x.rn > (int64_t)AU * NT) load(rb, tb, (int64_t)AU * NT, x.rn, x.nseg, x.segb);
+    if (x.rn > 0) load(ra, ta, 0u, x);
+    if (x.rn > (uint32_t)(AU * NT)) load(rb, tb, (uint32_t)(AU * NT), x);
   };
   // the bucket table (chunk starts, bucket bases) in LDS for every descriptor
   for (int k = threadIdx.x; k <= (1 << (q.log2P - q.fbits)); k += NT) {
@@ -1038,12 +1113,13 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
   for (int64_t w = blockIdx.x; w < nwork; w += gridDim.x) {
     const It it = nx;
     const uint32_t p = it.p;
-    const int sbits = it.sbits, sub = it.sub, nseg = it.nseg, segb = it.segb;
-    const int64_t rn = it.rn, nrow = it.nrow;
+    const int sbits = it.sbits, sub = it.sub;
+    const uint32_t rn = it.rn;
+    const int64_t nrow = it.nrow;
     const bool isel = it.isel;
     const int64_t wn = w + gridDim.x;
     if (wn < nwork) fetch(wn, pr);
-    if (first && threadIdx.x == 0) prn[p] = (uint32_t)rn;
+    if (first && threadIdx.x == 0) prn[p] = rn;
     if (rn == 0 && first) {  // untouched partition: nothing to rewrite
       if (wn < nwork) {
         prep(pr, nx);
@@ -1110,13 +1186,13 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
     // CASes are issued (prefetch): the chunk's segment lookups and the table-full flag then return
     // with the CASes (LDS returns in order), not behind this chunk's plane atomics, and the loads
     // have a whole chunk to land.  Returns false when the table is (about to be) full.
-    auto apply = [&](const uint64_t (&xr)[AU], const uint32_t (&txr)[AU], int64_t l0, auto R32, auto&& prefetch) -> bool {
+    auto apply = [&](const uint64_t (&xr)[AU], const uint32_t (&txr)[AU], uint32_t l0, auto R32, auto&& prefetch) -> bool {
       ID id[AU];
       uint32_t e[AU], tr[AU];
       bool pend[AU], claimed[AU];
 #pragma unroll
       for (int u = 0; u < AU; u++) {
-        const int64_t li = l0 + threadIdx.x + (int64_t)u * NT;
+        const uint32_t li = l0 + threadIdx.x + (uint32_t)(u * NT);
         const uint64_t v = xr[u];
         const int32_t t32 = WIDE ? (int32_t)txr[u] : (int32_t)(uint32_t)v;
         const uint64_t krel = v >> 32;
@@ -1141,8 +1217,9 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
         __hip_atomic_compare_exchange_strong(&ids[e[u]], &old[u], id[u], __ATOMIC_RELAXED, __ATOMIC_RELAXED,
                                              __HIP_MEMORY_SCOPE_WORKGROUP);
       }
-      const int full = *(volatile KLDS int*)&lovf;
+      const int fullv = *(volatile KLDS int*)&lovf;
       prefetch();
+      const int full = __builtin_amdgcn_readfirstlane(fullv);  // (one LDS word: the same in every lane)
 #pragma unroll
       for (int u = 0; u < AU; u++) {
         claimed[u] = id[u] != EMPTY && old[u] == EMPTY;
@@ -1186,15 +1263,16 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
       }
       return !full && nnow <= q.hmax;
     };
-    const int64_t nch = (rn + (int64_t)AU * NT - 1) / ((int64_t)AU * NT);
+    constexpr uint32_t CR = (uint32_t)(AU * NT);  // records per chunk
+    const uint32_t nch = (rn + CR - 1u) / CR;
     if (rn > 0) {  // chunks 0 and 1 are in flight (load01); each set is reloaded as it is applied
-      for (int64_t c = 0; c < nch; c += 2) {
-        auto pa = [&] { if (c + 2 < nch) load(ra, ta, (c + 2) * AU * NT, rn, nseg, segb); };
-        const bool ga = r32 ? apply(ra, ta, c * AU * NT, std::true_type{}, pa) : apply(ra, ta, c * AU * NT, std::false_type{}, pa);
+      for (uint32_t c = 0; c < nch; c += 2) {
+        auto pa = [&] { if (c + 2 < nch) load(ra, ta, (c + 2) * CR, it); };
+        const bool ga = r32 ? apply(ra, ta, c * CR, std::true_type{}, pa) : apply(ra, ta, c * CR, std::false_type{}, pa);
         if (!ga || c + 1 >= nch) break;
-        auto pb = [&] { if (c + 3 < nch) load(rb, tb, (c + 3) * AU * NT, rn, nseg, segb); };
-        const bool gb = r32 ? apply(rb, tb, (c + 1) * AU * NT, std::true_type{}, pb)
-                            : apply(rb, tb, (c + 1) * AU * NT, std::false_type{}, pb);
+        auto pb = [&] { if (c + 3 < nch) load(rb, tb, (c + 3) * CR, it); };
+        const bool gb = r32 ? apply(rb, tb, (c + 1) * CR, std::true_type{}, pb)
+                            : apply(rb, tb, (c + 1) * CR, std::false_type{}, pb);
         if (!gb) break;
       }
     }

@@ -13,12 +13,12 @@
 //   state   : deduplicated per input column: non-null count, sum (i64 / f64 bits),
 //             min / max as total-order int64 keys; one COUNT(*) word.
 //   dict    : UTF8 keys only — open-addressing dictionary → stable key id
-//             (= byte offset of the key's entry in an append-only arena).
+//             (= byte offset of the key's entry in an append-only arena): khip_dict.hip.
 //
 // Per micro-batch (all on the handle's stream):
 //   k_blockmax → k_scan_blocks : stream time before each 2048-record block
 //                                (exclusive prefix max, carried across batches)
-//   [UTF8] k_dict_probe → k_dict_commit → k_dict_resolve (khip_dict.hpp)
+//   [UTF8] k_dict_probe → k_dict_commit → k_dict_resolve (khip_dict.hip)
 //   k_apply     : in-block prefix max → late test → window fan-out → find-or-claim the
 //                 (key, ws) slot with one 64-bit CAS whose value references the batch
 //                 row (no spin, no fence) → agent-scope atomics for the state
@@ -518,416 +518,6 @@ __global__ __launch_bounds__(256) void k_off_resolve_probe(ApplyParams p, const 
   }
 }
 
-// ---------------------------------------------------------------- UTF8 dictionary (khip_dict.hpp)
-// Slot (32 B, one random access): w0 dict word: 0 empty | fresh: bit63 | fp22 << 40 | batch row
-// (40 bits) | resident: bit62 | fp22 << 40 | o / 8 (40 bits); w1 = o | min(len, 0xFFFF) << 48 (the
-// key's id = its arena offset o, and its length); w2, w3 = the key's first 16 bytes as words
-// (keys of up to 16 bytes compare there; longer ones against the arena entry).  Arena entry at o
-// (8-aligned): [u64 hash][i64 len][bytes, padded to 8].  A map is three passes, none over the
-// whole table:
-//   k_dict_probe    per row: hash, probe; a resident slot compares in place; an empty slot is
-//                   claimed (fresh word naming the row; the slot and its arena entry's place go to
-//                   one of DICT_NL claim lists, one block-aggregated append); a fresh slot of the same fingerprint, claimed by
-//                   another row of this batch, leaves the row PENDING on it
-//   k_dict_commit   per claim: the arena entry (its list's base + its place in the list), the slot
-//                   made resident with the key's words, the claiming row's id (no atomics)
-//   k_dict_resolve  per pending row: the (now resident) slot compares; a different key of the same
-//                   fingerprint goes on a retry list (probed again: the slot no longer misleads it)
-// A probe gives up after DICT_PROBE slots (the table is then too full: dict_map unclaims the
-// batch's fresh words, grows the table and maps the batch again).
-constexpr int DICT_PROBE = 256;
-constexpr uint64_t DICT_LOW = (1ULL << 40) - 1;
-constexpr int DICT_NL = 1024;  // claim lists (one per block residue: no hot append word)
-constexpr int64_t KID_PEND = (int64_t)1 << 62;
-constexpr uint64_t DICT_ID = (1ULL << 48) - 1;
-
-__device__ __forceinline__ int64_t entry_bytes(int64_t len) { return 16 + ((len + 7) & ~7LL); }
-
-#ifdef KHIP_TUNING
-// Tuning build: KHIP_DICT_HASHMASK keeps only these bits of every key hash (different keys then
-// share whole hashes, not just fingerprints: tests/test_gpu_dict.py); KHIP_KEY_INLINE=0 sends the
-// digit keys through the dictionary too.
-__constant__ uint64_t g_dict_hmask = ~0ULL;
-__constant__ int g_key_inline = 1;
-#endif
-
-// The key of batch row i: words (short keys), hash.
-struct DKey {
-  uint64_t kw[KW_MAX];
-  uint64_t h;
-  int64_t len;
-  const uint8_t* kb;
-  bool sk;
-};
-__device__ __forceinline__ void dkey_words(DKey& k, const int64_t* __restrict__ koff, const uint8_t* __restrict__ kbytes,
-                                           int64_t i) {
-  const int64_t o0 = koff[i];
-  k.len = koff[i + 1] - o0;
-  k.kb = kbytes + o0;
-  k.sk = k.len <= 8 * KW_MAX;
-  if (k.sk) key_words(k.kb, k.len, k.kw);
-}
-__device__ __forceinline__ void dkey_hash(DKey& k) {
-  k.h = k.sk ? hash_key_words(k.kw, k.len) : hash_bytes_dev(k.kb, k.len);
-#ifdef KHIP_TUNING
-  k.h &= g_dict_hmask;
-#endif
-}
-__device__ __forceinline__ void dkey_load(DKey& k, const int64_t* __restrict__ koff, const uint8_t* __restrict__ kbytes,
-                                          int64_t i) {
-  dkey_words(k, koff, kbytes, i);
-  dkey_hash(k);
-}
-
-// Key k's inline id (khip_dict.hpp), when it is 0..17 ASCII digits.
-__device__ __forceinline__ bool key_inline(const DKey& k, int64_t* code) {
-#ifdef KHIP_TUNING
-  if (!g_key_inline) return false;
-#endif
-  static_assert(KW_MAX == 3, "inline keys are read from three key words");
-  return k.sk && inline_id_words(k.kw, k.len, code);
-}
-
-// A resident slot (w0 fingerprint already matched) holds key k?
-__device__ __forceinline__ bool dslot_eq(const ulonglong2& a, const ulonglong2& b, const DKey& k,
-                                         const uint8_t* __restrict__ arena) {
-  const int64_t slen = (int64_t)(a.y >> 48);
-  if (k.len <= 16) return slen == k.len && b.x == k.kw[0] && b.y == (k.len > 8 ? k.kw[1] : 0ULL);
-  if (slen != (k.len < 0xFFFF ? k.len : 0xFFFF)) return false;
-  const int64_t o = (int64_t)(a.y & DICT_ID);
-  if (*(const uint64_t*)(arena + o) != k.h || *(const int64_t*)(arena + o + 8) != k.len) return false;
-  return k.sk ? key_words_eq_aligned(k.kw, arena + o + 16, k.len) : bytes_eq_aligned(arena + o + 16, k.kb, k.len);
-}
-
-// rows: null (row j = j) or a row list (the retry pass).  lists: DICT_NL regions of lcap entries
-// [slot | the entry's byte offset in its list << 34]; lw[L]: entries << 40 | entry bytes of list L.
-// nd[0] += the rows that probed (valid, not inline), nd[1] += the rows left pending (counted per
-// wave by ballots, summed per block in LDS at the end: one global atomic per block).
-__global__ __launch_bounds__(256) void k_dict_probe(ulonglong2* __restrict__ slots, uint64_t dmask,
-                                                    const uint8_t* __restrict__ arena, const int64_t* __restrict__ koff,
-                                                    const uint8_t* __restrict__ kbytes, const uint8_t* __restrict__ kv,
-                                                    const uint8_t* __restrict__ rv, const int64_t* __restrict__ ts,
-                                                    const int64_t* __restrict__ rows, int64_t n,
-                                                    int64_t* __restrict__ kid, int64_t* __restrict__ khash,
-                                                    uint64_t* __restrict__ lists, int64_t lcap,
-                                                    unsigned long long* __restrict__ lw, int* __restrict__ fail,
-                                                    uint64_t fpm, unsigned long long* __restrict__ nd) {
-  __shared__ unsigned long long wsum[4];  // per wave: claims << 40 | entry bytes
-  __shared__ unsigned long long bbase;
-  __shared__ unsigned long long bsum[2];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int L = blockIdx.x & (DICT_NL - 1);
-  if (threadIdx.x < 2) bsum[threadIdx.x] = 0;
-  unsigned long long bprobed = 0, bpend = 0;  // (the wave's counts over its tiles)
-  for (int64_t j0 = blockIdx.x * (int64_t)blockDim.x; j0 < n; j0 += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t j = j0 + threadIdx.x;
-    bool claimed = false, probed = false, pending = false;
-    uint64_t cslot = 0, eb = 0;
-    if (j < n) {
-      const int64_t i = rows ? rows[j] : j;
-      if (!(bit_get(kv, i) && bit_get(rv, i) && (ts == nullptr || ts[i] >= 0))) {
-        kid[i] = 0;
-        if (khash) khash[i] = 0;
-      } else {
-        DKey k;
-        dkey_words(k, koff, kbytes, i);
-        int64_t code;
-        const bool inl = key_inline(k, &code);
-        k.h = 0;
-        if (!inl) dkey_hash(k);
-        probed = !inl;
-        if (khash) khash[i] = inl ? code : (int64_t)k.h;
-        const uint64_t fp = (k.h >> 40) & fpm;
-        const uint64_t fresh = (1ULL << 63) | (fp << 40) | (uint64_t)i;
-        uint64_t slot = k.h & dmask;
-        bool done = inl;
-        if (inl) kid[i] = code;
-        for (int probe = 0; probe < DICT_PROBE && !done; probe++) {
-          ulonglong2 a = slots[2 * slot];  // a stale empty / fresh word is settled by the CAS below
-          uint64_t w = a.x;
-          if (w == 0) {
-            const uint64_t old = atomicCAS((unsigned long long*)&slots[2 * slot].x, 0ULL, (unsigned long long)fresh);
-            if (old == 0) {
-              kid[i] = -(int64_t)(slot + 1);  // commit writes the id
-              claimed = true;
-              cslot = slot;
-              eb = (uint64_t)entry_bytes(k.len);
-              done = true;
-              break;
-            }
-            w = old;
-          }
-          if (((w >> 40) & 0x3FFFFFULL) == fp) {
-            if (w >> 63) {  // claimed by another row of this batch: resolved after the commit
-              kid[i] = -(int64_t)(slot + 1) - KID_PEND;
-              pending = true;
-              done = true;
-            } else {
-              const ulonglong2 b = slots[2 * slot + 1];
-              if (a.x != w) a = slots[2 * slot];  // (the word moved on since the first read)
-              if (dslot_eq(a, b, k, arena)) {
-                kid[i] = (int64_t)(a.y & DICT_ID);
-                done = true;
-              }
-            }
-          }
-          if (!done) slot = (slot + 1) & dmask;
-        }
-        if (!done) {
-          kid[i] = 0;
-          *fail = 1;
-        }
-      }
-    }
-    bprobed += (unsigned long long)__popcll(__ballot(probed));
-    bpend += (unsigned long long)__popcll(__ballot(pending));
-    // the block's claims → list L: one atomic per block and tile for both the count and the bytes
-    const uint64_t x = claimed ? ((1ULL << 40) | eb) : 0ULL;
-    uint64_t incl = x;
-    for (int off = 1; off < 64; off <<= 1) {
-      const uint64_t y = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += y;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, tot = 0;
-    for (int k = 0; k < 4; k++) {
-      before += k < wave ? wsum[k] : 0;
-      tot += wsum[k];
-    }
-    if (threadIdx.x == 0) bbase = tot ? atomicAdd(&lw[L], (unsigned long long)tot) : 0ULL;
-    __syncthreads();
-    if (claimed) {
-      const uint64_t at = bbase + before + incl - x;  // this claim's entries << 40 | bytes before it
-      const uint64_t idx = at >> 40, boff = at & ((1ULL << 40) - 1);
-      if ((int64_t)idx < lcap && boff < (1ULL << 30)) lists[(uint64_t)L * lcap + idx] = cslot | (boff << 34);
-      else *fail = 2;  // (lcap covers every row a list's blocks can claim)
-    }
-  }
-  __syncthreads();
-  if (lane == 0 && bprobed) atomicAdd(&bsum[0], bprobed);
-  if (lane == 0 && bpend) atomicAdd(&bsum[1], bpend);
-  __syncthreads();
-  if (threadIdx.x < 2 && bsum[threadIdx.x]) atomicAdd(&nd[threadIdx.x], bsum[threadIdx.x]);
-}
-
-// The inline ids of a batch, before any dictionary work: rows without a key get 0, inline keys
-// their id (khash: the id), other keys KID_DICT; nd[0] += the rows left for the dictionary, nd[1]
-// += the inline rows (one atomic per block each; ts is not read: a late row's id is never used).
-// Branch-free loads, R rows per thread: every row's offsets, then every row's first four aligned
-// key words (clamped to the words that hold its bytes, so no load leaves the key column; an empty
-// key reads the word of the column's first byte, or nothing when the column is empty), then the
-// SWAR check per row.
-constexpr int64_t KID_DICT = INT64_MIN;
-template <int R>
-__global__ __launch_bounds__(256) void k_key_inline(const int64_t* __restrict__ koff, const uint8_t* __restrict__ kbytes,
-                                                    const uint8_t* __restrict__ kv, const uint8_t* __restrict__ rv,
-                                                    const int64_t* __restrict__ ts, int64_t n, int64_t* __restrict__ kid,
-                                                    int64_t* __restrict__ khash, unsigned long long* __restrict__ nd) {
-  (void)ts;
-  const int64_t kfirst = koff[0];
-  const bool has_bytes = koff[n] > kfirst;
-  const uint8_t* anchor = kbytes + kfirst;  // (a byte of the column when has_bytes)
-  __shared__ unsigned int bsum[2];
-  if (threadIdx.x < 2) bsum[threadIdx.x] = 0;
-  unsigned int cnt = 0, ninl = 0;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t j0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j0 < n; j0 += stride * R) {
-    int64_t o0[R], len[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-      const int64_t i = j0 + r * stride < n ? j0 + r * stride : n - 1;
-      o0[r] = koff[i];
-      len[r] = koff[i + 1] - o0[r];
-    }
-    uint64_t A[R][KW_MAX + 1];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-      const uint8_t* p = kbytes + o0[r];
-      const int64_t lb = len[r] < 8 * KW_MAX ? len[r] : 8 * KW_MAX;  // (longer keys are never inline)
-      const uint64_t a = (uint64_t)p;
-      const uint64_t* base = (const uint64_t*)(p - (a & 7));
-      const int last = lb > 0 ? (int)(((a & 7) + (uint64_t)lb - 1) >> 3) : 0;
-      const uint64_t* b0 = lb > 0 ? base : (const uint64_t*)(anchor - ((uint64_t)anchor & 7));
-#pragma unroll
-      for (int k = 0; k <= KW_MAX; k++) A[r][k] = has_bytes ? b0[k < last ? k : last] : 0ULL;
-    }
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-      const int64_t i = j0 + r * stride;
-      if (i >= n) break;
-      int64_t code = 0;
-      if (bit_get(kv, i) && bit_get(rv, i)) {
-        // key_words from the loaded aligned words
-        const uint64_t a = (uint64_t)(kbytes + o0[r]);
-        const int sh = (int)(a & 7) * 8;
-        DKey k;
-        k.len = len[r];
-        k.sk = k.len <= 8 * KW_MAX;
-#pragma unroll
-        for (int q = 0; q < KW_MAX; q++) {
-          uint64_t x = sh ? (A[r][q] >> sh) | (A[r][q + 1] << (64 - sh)) : A[r][q];
-          const int64_t left = k.len - 8 * q;
-          if (left <= 0) x = 0;
-          else if (left < 8) x &= (1ULL << (8 * left)) - 1;
-          k.kw[q] = x;
-        }
-        if (key_inline(k, &code)) {
-          ninl++;
-        } else {
-          code = KID_DICT;
-          cnt++;
-        }
-      }
-      kid[i] = code;
-      if (khash) khash[i] = code;
-    }
-  }
-  __syncthreads();
-  if (cnt) atomicAdd(&bsum[0], cnt);
-  if (ninl) atomicAdd(&bsum[1], ninl);
-  __syncthreads();
-  if (threadIdx.x < 2 && bsum[threadIdx.x]) atomicAdd(&nd[threadIdx.x], (unsigned long long)bsum[threadIdx.x]);
-}
-
-// The lists' arena bases after a probe round (one block, a thread per list): lbase[L] = the arena's
-// used bytes + the entry bytes of the lists before L; the used bytes and the key count advance.
-// Nothing when the round failed (c's first word: the probe's failure flag).
-__global__ __launch_bounds__(1024) void k_dict_bases(unsigned long long* __restrict__ c,
-                                                     const unsigned long long* __restrict__ lw,
-                                                     int64_t* __restrict__ lbase) {
-  static_assert(DICT_NL == 1024, "a thread per list");
-  __shared__ unsigned long long ws[16], wk[16];
-  if (*(const volatile int*)c != 0) return;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const unsigned long long x = lw[t];
-  const unsigned long long by = x & ((1ULL << 40) - 1), ke = x >> 40;
-  unsigned long long incl = by, kin = ke;
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned long long y = __shfl_up(incl, off, 64), z = __shfl_up(kin, off, 64);
-    if (lane >= off) {
-      incl += y;
-      kin += z;
-    }
-  }
-  if (lane == 63) {
-    ws[wave] = incl;
-    wk[wave] = kin;
-  }
-  __syncthreads();
-  unsigned long long before = 0, tot = 0, ktot = 0;
-  for (int k = 0; k < 16; k++) {
-    before += k < wave ? ws[k] : 0ULL;
-    tot += ws[k];
-    ktot += wk[k];
-  }
-  lbase[t] = (int64_t)(c[1] + before + incl - by);
-  __syncthreads();  // (every thread has read c[1])
-  if (t == 0) {
-    c[1] += tot;
-    c[2] += ktot;
-  }
-}
-
-// One thread per claim (list L, entries t, t + stride, ...): the arena entry at its list's base +
-// its byte offset, the slot made resident with the key's words, the claiming row's id.  lbase[L]:
-// the list's arena base.  Nothing when the round failed.
-__global__ __launch_bounds__(256) void k_dict_commit(ulonglong2* __restrict__ slots, const uint64_t* __restrict__ lists,
-                                                     int64_t lcap, const unsigned long long* __restrict__ lw,
-                                                     const int64_t* __restrict__ lbase, uint8_t* __restrict__ arena,
-                                                     const int64_t* __restrict__ koff, const uint8_t* __restrict__ kbytes,
-                                                     int64_t* __restrict__ kid, const unsigned long long* __restrict__ c) {
-  if (*(const volatile int*)c != 0) return;
-  const int L = blockIdx.y;
-  const int64_t cntL = (int64_t)(lw[L] >> 40);
-  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < cntL; t += (int64_t)gridDim.x * blockDim.x) {
-  const uint64_t le = lists[(uint64_t)L * lcap + t];
-  const uint64_t slot = le & ((1ULL << 34) - 1);
-  const uint64_t w = slots[2 * slot].x;
-  const int64_t r = (int64_t)(w & DICT_LOW);
-  DKey k;
-  dkey_load(k, koff, kbytes, r);
-  const int64_t o = lbase[L] + (int64_t)(le >> 34);
-  *(uint64_t*)(arena + o) = k.h;
-  *(int64_t*)(arena + o + 8) = k.len;
-  if (k.sk) {
-    for (int q = 0; q < (int)((k.len + 7) >> 3); q++) ((uint64_t*)(arena + o + 16))[q] = k.kw[q];
-  } else {
-    for (int64_t b = 0; b < k.len; b++) arena[o + 16 + b] = k.kb[b];
-  }
-  const uint64_t fp = (w >> 40) & 0x3FFFFFULL;
-  const uint64_t lenw = (uint64_t)(k.len < 0xFFFF ? k.len : 0xFFFF) << 48;
-  slots[2 * slot + 1] = make_ulonglong2(k.len <= 16 ? k.kw[0] : 0ULL, k.len <= 16 && k.len > 8 ? k.kw[1] : 0ULL);
-  slots[2 * slot] = make_ulonglong2((1ULL << 62) | (fp << 40) | ((uint64_t)o >> 3), (uint64_t)o | lenw);
-  kid[r] = o;
-  }
-}
-
-// Rows left pending on a slot another row claimed: the slot is resident now.  A different key of
-// the same fingerprint goes on the retry list.
-__global__ __launch_bounds__(256) void k_dict_resolve(const ulonglong2* __restrict__ slots,
-                                                      const uint8_t* __restrict__ arena,
-                                                      const int64_t* __restrict__ koff,
-                                                      const uint8_t* __restrict__ kbytes, const int64_t* __restrict__ rows,
-                                                      int64_t n, int64_t* __restrict__ kid,
-                                                      int64_t* __restrict__ retry, unsigned long long* __restrict__ nretry,
-                                                      const unsigned long long* __restrict__ c,
-                                                      const unsigned long long* __restrict__ npend) {
-  if (*(const volatile int*)c != 0 || *npend == 0) return;  // (a failed round, or no row pending)
-  for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t i = rows ? rows[j] : j;
-    const int64_t x = kid[i];
-    if (x >= -KID_PEND) continue;  // an id, or the claimer's (written by the commit)
-    const uint64_t slot = (uint64_t)(-(x + KID_PEND) - 1);
-    DKey k;
-    dkey_load(k, koff, kbytes, i);
-    const ulonglong2 a = slots[2 * slot], b = slots[2 * slot + 1];
-    if (dslot_eq(a, b, k, arena)) {
-      kid[i] = (int64_t)(a.y & DICT_ID);
-    } else {
-      kid[i] = 0;
-      retry[atomicAdd(nretry, 1ULL)] = i;
-    }
-  }
-}
-
-// Read-only dictionary probe (pull queries, join probes): key bytes → resident key id (arena
-// offset), or -1 when the key was never seen.  Every slot is resident between maps.
-__global__ __launch_bounds__(256) void k_dict_find(const ulonglong2* __restrict__ slots, uint64_t dmask,
-                                                   const uint8_t* __restrict__ arena,
-                                                   const int64_t* __restrict__ koff, const uint8_t* __restrict__ kbytes,
-                                                   int64_t n, int64_t* __restrict__ kid, uint64_t fpm) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    DKey k;
-    dkey_words(k, koff, kbytes, i);
-    int64_t code;
-    if (key_inline(k, &code)) {
-      kid[i] = code;
-      continue;
-    }
-    dkey_hash(k);
-    const uint64_t fp = (k.h >> 40) & fpm;
-    uint64_t slot = k.h & dmask;
-    int64_t found = -1;
-    for (int probe = 0; probe <= (int)dmask && probe < (1 << 20); probe++) {
-      const ulonglong2 a = slots[2 * slot];
-      if (a.x == 0) break;
-      if (((a.x >> 40) & 0x3FFFFFULL) == fp && dslot_eq(a, slots[2 * slot + 1], k, arena)) {
-        found = (int64_t)(a.y & DICT_ID);
-        break;
-      }
-      slot = (slot + 1) & dmask;
-    }
-    kid[i] = found;
-  }
-}
-
-// A failed map: the batch's fresh claims → empty (the table is as before the batch).
-__global__ __launch_bounds__(256) void k_dict_unclaim(ulonglong2* __restrict__ slots, int64_t dcap) {
-  for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < dcap; s += (int64_t)gridDim.x * blockDim.x)
-    if (slots[2 * s].x >> 63) slots[2 * s] = make_ulonglong2(0ULL, 0ULL);
-}
-
 // Exclusive prefix sum of v[0..n) in place (single block); total added to *total.  Each thread
 // owns 16 consecutive elements of a 16K-element chunk: one wave scan and one barrier per chunk.
 __global__ __launch_bounds__(1024) void k_scan_excl(int64_t* __restrict__ v, int64_t n, int64_t* __restrict__ total) {
@@ -966,212 +556,9 @@ __global__ __launch_bounds__(1024) void k_scan_excl(int64_t* __restrict__ v, int
   if (threadIdx.x == 0) *total += carry;
 }
 
-__global__ __launch_bounds__(256) void k_dict_rehash(const ulonglong2* __restrict__ os, int64_t ocap,
-                                                     ulonglong2* __restrict__ ns, uint64_t nmask,
-                                                     const uint8_t* __restrict__ arena) {
-  for (int64_t s = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; s < ocap; s += (int64_t)gridDim.x * blockDim.x) {
-    const ulonglong2 a = os[2 * s];
-    if (a.x == 0) continue;
-    const uint64_t h = *(const uint64_t*)(arena + (a.y & DICT_ID));
-    uint64_t d = h & nmask;
-    while (atomicCAS((unsigned long long*)&ns[2 * d].x, 0ULL, (unsigned long long)a.x) != 0ULL) d = (d + 1) & nmask;
-    ns[2 * d + 1] = os[2 * s + 1];
-    ns[2 * d].y = a.y;
-  }
-}
+}  // namespace khip
 
 // ------------------------------------------------------------------- host side
-
-static int grid_for(int64_t work, int per_block, int cap_blocks = 2048 * 8) {
-  int64_t g = ceil_div(std::max<int64_t>(work, 1), per_block);
-  return (int)std::min<int64_t>(g, cap_blocks);
-}
-
-// ---- KeyDict (khip_dict.hpp)
-
-// The fingerprint bits a probe compares before the key (22; the tuning build's KHIP_DICT_FPMASK
-// narrows them so that different keys meet on claimed slots: the pending / retry rounds).
-static uint64_t dict_fp_mask() { return (uint64_t)knob("KHIP_DICT_FPMASK", 0x3FFFFF) & 0x3FFFFFULL; }
-
-static khip_status dict_grow(KeyDict& d, hipStream_t s, int64_t new_cap) {
-  DevBuf ns;
-  KHIP_TRY(ns.ensure((size_t)new_cap * 32));
-  KHIP_TRY_HIP(hipMemsetAsync(ns.p, 0, (size_t)new_cap * 32, s));
-  if (d.dcap > 0 && d.docc > 0) {
-    hipLaunchKernelGGL(k_dict_rehash, dim3(grid_for(d.dcap, 256)), dim3(256), 0, s, d.slots.as<ulonglong2>(), d.dcap,
-                       ns.as<ulonglong2>(), (uint64_t)(new_cap - 1), d.arena.as<uint8_t>());
-    KHIP_TRY_HIP(hipGetLastError());
-  }
-  KHIP_TRY_HIP(hipStreamSynchronize(s));
-  d.slots.release();
-  d.slots = std::move(ns);
-  ns.p = nullptr;
-  d.dcap = new_cap;
-  return KHIP_OK;
-}
-
-khip_status dict_init(KeyDict& d, hipStream_t s) {
-#ifdef KHIP_TUNING
-  const uint64_t hm = (uint64_t)knob("KHIP_DICT_HASHMASK", -1);
-  KHIP_TRY_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_dict_hmask), &hm, 8));
-  const int inl = (int)knob("KHIP_KEY_INLINE", 1);
-  KHIP_TRY_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_key_inline), &inl, 4));
-#endif
-  KHIP_TRY(d.ctr.ensure(64 + 16 * DICT_NL));  // (dict_round's counters)
-  return dict_grow(d, s, 4096);
-}
-
-// One round over `rows` (null: every row): probe, commit the claims, resolve the pending rows.
-// Returns the rows to retry (a different key behind a pending row's fingerprint) in d.retry,
-// their count in *nretry; *failed when a probe ran out of budget (nothing committed then).
-// Counters (d.ctr, u64): [0] probe failure | [1] arena bytes used | [2] keys added | [3] retries |
-// [4 ..] DICT_NL list words | then DICT_NL list arena bases | rows probed | rows pending.
-static khip_status dict_round(KeyDict& d, hipStream_t s, const int64_t* koff, const uint8_t* kbytes, const uint8_t* kv,
-                              const uint8_t* rv, const int64_t* ts, const int64_t* rows, int64_t n, int64_t* kid,
-                              int64_t* khash, int64_t* nretry, bool* failed) {
-  unsigned long long* c = d.ctr.as<unsigned long long>();
-  unsigned long long* lw = c + 4;
-  int64_t* lbase = (int64_t*)(c + 4 + DICT_NL);
-  unsigned long long* nd = c + 4 + 2 * DICT_NL;
-  const int g = grid_for(n, 256);
-  // a list takes the claims of blocks L, L + DICT_NL, ...: at most every row those blocks visit
-  const int64_t lcap = ceil_div(g, DICT_NL) * 256 * ceil_div(n, 256LL * g);
-  KHIP_TRY(d.lists.ensure((size_t)lcap * DICT_NL * 8));
-  KHIP_TRY(d.retry.ensure((size_t)std::max<int64_t>(n, 1) * 8));
-  KHIP_TRY_HIP(hipMemsetAsync(c, 0, 8, s));
-  KHIP_TRY_HIP(hipMemsetAsync(c + 3, 0, 8 + 8 * DICT_NL, s));
-  KHIP_TRY_HIP(hipMemsetAsync(nd, 0, 16, s));
-  // probe → list bases → commit → resolve, with no host round trip in between: each later kernel
-  // does nothing when the probe failed (the table is grown and the round mapped again)
-  hipLaunchKernelGGL(k_dict_probe, dim3(g), dim3(256), 0, s, d.slots.as<ulonglong2>(), (uint64_t)(d.dcap - 1),
-                     d.arena.as<uint8_t>(), koff, kbytes, kv, rv, ts, rows, n, kid, khash, d.lists.as<uint64_t>(), lcap,
-                     lw, (int*)c, dict_fp_mask(), nd);
-  hipLaunchKernelGGL(k_dict_bases, dim3(1), dim3(DICT_NL), 0, s, c, (const unsigned long long*)lw, lbase);
-  hipLaunchKernelGGL(k_dict_commit, dim3((unsigned)std::min<int64_t>(4, ceil_div(lcap, 256LL)), DICT_NL), dim3(256), 0,
-                     s, d.slots.as<ulonglong2>(), d.lists.as<uint64_t>(), lcap, lw, lbase, d.arena.as<uint8_t>(), koff,
-                     kbytes, kid, (const unsigned long long*)c);
-  hipLaunchKernelGGL(k_dict_resolve, dim3(g), dim3(256), 0, s, d.slots.as<ulonglong2>(), d.arena.as<uint8_t>(), koff,
-                     kbytes, rows, n, kid, d.retry.as<int64_t>(), c + 3, (const unsigned long long*)c,
-                     (const unsigned long long*)(nd + 1));
-  KHIP_TRY_HIP(hipGetLastError());
-  unsigned long long h[6];
-  KHIP_TRY_HIP(hipMemcpyAsync(h, c, 32, hipMemcpyDeviceToHost, s));
-  KHIP_TRY_HIP(hipMemcpyAsync(h + 4, nd, 16, hipMemcpyDeviceToHost, s));
-  KHIP_TRY_HIP(hipStreamSynchronize(s));
-  *failed = (h[0] & 0xFFFFFFFFULL) != 0;
-  d.round_probed = (int64_t)h[4];
-  if (!rows) d.last_probed = d.round_probed;  // (the first round sees every row)
-  *nretry = *failed ? 0 : (int64_t)h[3];
-  if (!*failed) {  // (cumulative over the map's rounds)
-    d.round_used = (int64_t)h[1];
-    d.round_keys = (int64_t)h[2];
-  }
-  return KHIP_OK;
-}
-
-khip_status dict_map(KeyDict& d, hipStream_t s, const int64_t* koff, const uint8_t* kbytes, int64_t key_bytes_total,
-                     const uint8_t* kv, const uint8_t* rv, const int64_t* ts, int64_t n, int64_t* kid, int64_t* khash) {
-  // inline ids first: a batch whose keys are all inline (or invalid) never touches the dictionary.
-  // (Skipped while the maps find no inline key at all — the probe turns inline keys into their ids
-  // too — and tried again every 16th map.)
-  if (d.last_inline != 0 || (++d.maps & 15) == 0) {
-    unsigned long long* nd = d.ctr.as<unsigned long long>() + 4 + 2 * DICT_NL + 2;
-    KHIP_TRY_HIP(hipMemsetAsync(nd, 0, 16, s));
-    // rows per thread (1 / 2 / 4 / 8: 751 / 740 / 807 / 982 us on C2 --utf8, profiles/r05/ab/inline_rows.txt)
-    const int ir = (int)knob("KHIP_INLINE_R", 2);
-    auto ik = ir >= 8 ? k_key_inline<8> : (ir >= 4 ? k_key_inline<4> : (ir >= 2 ? k_key_inline<2> : k_key_inline<1>));
-    hipLaunchKernelGGL(ik, dim3(grid_for(ceil_div(n, (int64_t)std::max(ir, 1)), 256, 4096)), dim3(256), 0, s, koff, kbytes, kv,
-                       rv, ts, n, kid, khash, nd);
-    KHIP_TRY_HIP(hipGetLastError());
-    unsigned long long h[2] = {0, 0};
-    KHIP_TRY_HIP(hipMemcpyAsync(h, nd, 16, hipMemcpyDeviceToHost, s));
-    KHIP_TRY_HIP(hipStreamSynchronize(s));
-    d.last_inline = (int64_t)h[1];
-    if (h[0] == 0) {
-      d.last_probed = d.round_probed = 0;
-      if (d.last_added < 0) d.last_added = 0;
-      return KHIP_OK;
-    }
-  }
-  // room for the keys this batch may add at load <= 1/2: an eighth of the rows on the first map,
-  // then twice the last map's new keys (at least 1/16 of the rows that reached the dictionary:
-  // inline keys never do) — a batch that brings more fails its probes and is mapped again into a
-  // larger table, so the table tracks the key count, not the batch size
-  const int64_t est =
-      d.last_added < 0 ? std::max<int64_t>(n / 8, 4096)
-                       : std::min<int64_t>(n, std::max<int64_t>({2 * d.last_added, std::min(n, d.last_probed) / 16, 4096}));
-  if (2 * (d.docc + est) > d.dcap) KHIP_TRY(dict_grow(d, s, next_pow2(2 * (d.docc + est))));
-  const int64_t need = d.arena_used + key_bytes_total + 16 * n + 16;
-  if ((size_t)need > d.arena.bytes) {
-    DevBuf na;
-    KHIP_TRY(na.ensure((size_t)std::max<int64_t>(need * 2, 1 << 20)));
-    if (d.arena_used) KHIP_TRY_HIP(hipMemcpyAsync(na.p, d.arena.p, d.arena_used, hipMemcpyDeviceToDevice, s));
-    KHIP_TRY_HIP(hipStreamSynchronize(s));
-    d.arena.release();
-    d.arena = std::move(na);
-    na.p = nullptr;
-  }
-  unsigned long long* c = d.ctr.as<unsigned long long>();
-  const unsigned long long start[3] = {0ULL, (unsigned long long)d.arena_used, 0ULL};
-  KHIP_TRY_HIP(hipMemcpyAsync(c, start, 24, hipMemcpyHostToDevice, s));
-  d.round_used = d.arena_used;
-  d.round_keys = 0;
-  const int64_t* rows = nullptr;
-  int64_t m = n;
-  DevBuf rl;  // a retry round's rows (the previous round's retry list)
-  for (int round = 0, grown = 0; m > 0; round++) {
-    int64_t nretry = 0;
-    bool failed = false;
-    KHIP_TRY(dict_round(d, s, koff, kbytes, kv, rv, ts, rows, m, kid, khash, &nretry, &failed));
-    if (failed) {  // undo this round's claims, grow, and map its rows again
-      if (++grown > 6 || d.dcap >= ((int64_t)1 << 34)) return fail(KHIP_E_DEVICE, "key dictionary probe budget exhausted");
-      hipLaunchKernelGGL(k_dict_unclaim, dim3(grid_for(d.dcap, 256)), dim3(256), 0, s, d.slots.as<ulonglong2>(), d.dcap);
-      KHIP_TRY_HIP(hipGetLastError());
-      // (room for every row that probed, as distinct keys, at load <= 1/2)
-      KHIP_TRY(dict_grow(d, s, std::max<int64_t>(d.dcap * 4, next_pow2(2 * (d.docc + d.round_probed)))));
-      continue;
-    }
-    if (round > 64) return fail(KHIP_E_DEVICE, "key dictionary: rows unresolved after 64 rounds");
-    if (nretry == 0) break;
-    KHIP_TRY(rl.ensure((size_t)nretry * 8));
-    KHIP_TRY_HIP(hipMemcpyAsync(rl.p, d.retry.p, (size_t)nretry * 8, hipMemcpyDeviceToDevice, s));
-    rows = rl.as<int64_t>();
-    m = nretry;
-  }
-  d.arena_used = d.round_used;
-  d.docc += d.round_keys;
-  d.last_added = d.round_keys;
-  return KHIP_OK;
-}
-
-khip_status dict_find(KeyDict& d, hipStream_t s, const int64_t* koff, const uint8_t* kbytes, int64_t n, int64_t* kid) {
-  if (n <= 0) return KHIP_OK;
-  hipLaunchKernelGGL(k_dict_find, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, d.slots.as<ulonglong2>(),
-                     (uint64_t)(d.dcap - 1), d.arena.as<uint8_t>(), koff, kbytes, n, kid, dict_fp_mask());
-  KHIP_TRY_HIP(hipGetLastError());
-  return KHIP_OK;
-}
-
-khip_status dict_clear(KeyDict& d, hipStream_t s) {
-  // the next batches likely bring as many keys as the dictionary held: a table far larger than
-  // that (sized by a first map's every-row estimate) is given back
-  const int64_t held = d.docc;
-  const int64_t keep = std::max<int64_t>(4096, next_pow2(4 * std::max<int64_t>(held, 1)));
-  d.docc = 0;
-  if (d.dcap >= 4 * keep) KHIP_TRY(dict_grow(d, s, keep));
-  if (d.dcap) KHIP_TRY_HIP(hipMemsetAsync(d.slots.p, 0, d.dcap * 32, s));
-  if (held > 0) d.last_added = held;  // the next map re-inserts about as many
-  d.arena_used = 0;
-  return KHIP_OK;
-}
-
-void dict_release(KeyDict& d) {
-  DevBuf* bufs[] = {&d.slots, &d.arena, &d.ctr, &d.lists, &d.retry};
-  for (DevBuf* b : bufs) b->release();
-  d.dcap = d.docc = d.arena_used = 0;
-}
-
-}  // namespace khip
 
 using namespace khip;
 
@@ -1425,8 +812,6 @@ khip_status khip::agg_grow_table(khip_agg* a, int64_t new_cap) {
   return KHIP_OK;
 }
 
-static khip_status grow_table(khip_agg* a, int64_t new_cap) { return agg_grow_table(a, new_cap); }
-
 namespace khip {
 
 int64_t visible_from(const khip_agg* a) {
@@ -1447,9 +832,9 @@ int64_t visible_from(const khip_agg* a) {
 }
 
 // EMIT FINAL: the window starts this batch closes after they expired (k_emit_lost), computed from
-// the batch alone before the engine runs; collected by finish_lost() after the push's sync.
+// the batch alone before the engine runs; collected by finish_lost_seed() after the push's sync.
 khip_status emit_final_lost(khip_agg* a, const int64_t* ts, const uint8_t* kv, const uint8_t* rv, int64_t n,
-                            int64_t seed_st, const int64_t*) {
+                            int64_t seed_st) {
   const int64_t nb = ceil_div(n, RPB);
   KHIP_TRY(a->blockmax.ensure(nb * 8));
   KHIP_TRY(a->blockprefix.ensure(nb * 8 + 8));
@@ -1475,39 +860,6 @@ khip_status emit_final_lost(khip_agg* a, const int64_t* ts, const uint8_t* kv, c
   return KHIP_OK;
 }
 
-// After the push's sync: the lost ranges → host (sorted, merged); re-run with room if the
-// buffer overflowed (the batch is still valid: the caller owns it until the push returns).
-static khip_status finish_lost_seed(khip_agg* a, const int64_t* ts, const uint8_t* kv, const uint8_t* rv, int64_t n,
-                                   int64_t seed_st) {
-  int64_t cnt = 0;
-  KHIP_TRY_HIP(hipMemcpy(&cnt, a->lostctr.p, 8, hipMemcpyDeviceToHost));
-  if (cnt > a->lost_cap) {
-    a->lost_cap = next_pow2(cnt);
-    a->lostbuf.release();
-    KHIP_TRY(a->lostbuf.ensure((size_t)a->lost_cap * 16));
-    KHIP_TRY(emit_final_lost(a, ts, kv, rv, n, seed_st, nullptr));
-    KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
-    KHIP_TRY_HIP(hipMemcpy(&cnt, a->lostctr.p, 8, hipMemcpyDeviceToHost));
-  }
-  std::vector<std::pair<int64_t, int64_t>> r((size_t)cnt);
-  if (cnt) KHIP_TRY_HIP(hipMemcpy(r.data(), a->lostbuf.p, (size_t)cnt * 16, hipMemcpyDeviceToHost));
-  std::sort(r.begin(), r.end());
-  a->lost.clear();
-  for (auto& x : r) {
-    if (!a->lost.empty() && x.first <= a->lost.back() + 1) {
-      a->lost.back() = std::max(a->lost.back(), x.second);
-    } else {
-      a->lost.push_back(x.first);
-      a->lost.push_back(x.second);
-    }
-  }
-  return KHIP_OK;
-}
-
-static khip_status finish_lost(khip_agg* a, const int64_t* ts, const uint8_t* kv, const uint8_t* rv, int64_t n) {
-  return finish_lost_seed(a, ts, kv, rv, n, a->st_before);
-}
-
 // Sorted [lo, hi] pairs, overlapping or adjacent ones merged.
 static std::vector<int64_t> merge_ranges(std::vector<std::pair<int64_t, int64_t>> r) {
   std::sort(r.begin(), r.end());
@@ -1521,6 +873,26 @@ static std::vector<int64_t> merge_ranges(std::vector<std::pair<int64_t, int64_t>
     }
   }
   return out;
+}
+
+// After the push's sync: the lost ranges → host (sorted, merged); re-run with room if the
+// buffer overflowed (the batch is still valid: the caller owns it until the push returns).
+static khip_status finish_lost_seed(khip_agg* a, const int64_t* ts, const uint8_t* kv, const uint8_t* rv, int64_t n,
+                                   int64_t seed_st) {
+  int64_t cnt = 0;
+  KHIP_TRY_HIP(hipMemcpy(&cnt, a->lostctr.p, 8, hipMemcpyDeviceToHost));
+  if (cnt > a->lost_cap) {
+    a->lost_cap = next_pow2(cnt);
+    a->lostbuf.release();
+    KHIP_TRY(a->lostbuf.ensure((size_t)a->lost_cap * 16));
+    KHIP_TRY(emit_final_lost(a, ts, kv, rv, n, seed_st));
+    KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
+    KHIP_TRY_HIP(hipMemcpy(&cnt, a->lostctr.p, 8, hipMemcpyDeviceToHost));
+  }
+  std::vector<std::pair<int64_t, int64_t>> r((size_t)cnt);
+  if (cnt) KHIP_TRY_HIP(hipMemcpy(r.data(), a->lostbuf.p, (size_t)cnt * 16, hipMemcpyDeviceToHost));
+  a->lost = merge_ranges(std::move(r));
+  return KHIP_OK;
 }
 
 }  // namespace khip
@@ -1735,66 +1107,156 @@ static khip_status stage(khip_agg* a, DevBuf& buf, const void* src, size_t bytes
   return KHIP_OK;
 }
 
+// The device-side view of one batch: what the push's stages hand to each other.  It lives on the
+// entry point's stack; resolve_batch fills the columns, the later stages the rest.
+struct BatchIn {
+  int64_t n = 0;
+  const int64_t* keys = nullptr;   // GROUP BY keys: the INT64 column, or the UTF8 keys' ids (key_ids)
+  const int64_t* hkeys = nullptr;  // what the hashing engines hash: keys, or the UTF8 keys' hashes
+  const int64_t* ts = nullptr;
+  const uint8_t *kv = nullptr, *rv = nullptr;
+  const int64_t* koff = nullptr;  // UTF8 keys: offsets[n + 1] into kbytes
+  const uint8_t* kbytes = nullptr;
+  int64_t key_bytes_total = 0;    // = koff[n] (a device batch: valid after the next synchronisation)
+  ColPtrs cols{};                 // the user columns, then the hidden sequence columns
+  const int64_t* st_at = nullptr;  // ABI 5 domains: the stream time observed at every row
+  const int32_t* part = nullptr;   // KHIP_TIME_PARTITION: every row's source partition
+};
+
+// n, ts, key_valid and row_valid of a batch: a host batch's are staged into the handle's buffers
+// (asynchronously, on its stream), a device batch's are used where they lie.
+static khip_status stage_ts_valid(khip_agg* a, const khip_batch* b, BatchIn& in) {
+  in.n = b->n_rows;
+  in.ts = b->ts;
+  in.kv = b->key_valid;
+  in.rv = b->row_valid;
+  if (b->mem == KHIP_MEM_DEVICE) return KHIP_OK;
+  if (b->mem != KHIP_MEM_HOST) return fail(KHIP_E_INVALID, "batch mem");
+  const size_t bm = (size_t)(in.n + 7) / 8;
+  KHIP_TRY(stage(a, a->st_ts, b->ts, in.n * 8));
+  in.ts = a->st_ts.as<int64_t>();
+  if (in.kv) { KHIP_TRY(stage(a, a->st_kv, in.kv, bm)); in.kv = a->st_kv.as<uint8_t>(); }
+  if (in.rv) { KHIP_TRY(stage(a, a->st_rv, in.rv, bm)); in.rv = a->st_rv.as<uint8_t>(); }
+  return KHIP_OK;
+}
+
 // The batch's device pointers: host batches are staged into the handle's buffers (asynchronously,
 // on its stream); UTF8 key byte totals of device batches are fetched (synchronise before use).
-static khip_status resolve_batch(khip_agg* a, const khip_batch* b, const int64_t** keys_o, const int64_t** ts_o,
-                                 const uint8_t** kv_o, const uint8_t** rv_o, const int64_t** koff_o,
-                                 const uint8_t** kbytes_o, ColPtrs* cols_o, int64_t* key_bytes_total_o) {
-  const int64_t n = b->n_rows;
+static khip_status resolve_batch(khip_agg* a, const khip_batch* b, BatchIn& in) {
+  KHIP_TRY(stage_ts_valid(a, b, in));
+  const int64_t n = in.n;
   const bool utf8 = a->desc.key_type == KHIP_KEY_UTF8;
-  const int64_t* keys = b->key_i64;
-  const int64_t* ts = b->ts;
-  const uint8_t* kv = b->key_valid;
-  const uint8_t* rv = b->row_valid;
-  const int64_t* koff = b->key_offsets;
-  const uint8_t* kbytes = b->key_bytes;
-  ColPtrs cols{};
-  const size_t bm = (size_t)(n + 7) / 8;
-  int64_t key_bytes_total = 0;
+  in.keys = b->key_i64;
+  in.koff = b->key_offsets;
+  in.kbytes = b->key_bytes;
   if (b->mem == KHIP_MEM_HOST) {
-    KHIP_TRY(stage(a, a->st_ts, b->ts, n * 8));
-    ts = a->st_ts.as<int64_t>();
-    if (kv) { KHIP_TRY(stage(a, a->st_kv, kv, bm)); kv = a->st_kv.as<uint8_t>(); }
-    if (rv) { KHIP_TRY(stage(a, a->st_rv, rv, bm)); rv = a->st_rv.as<uint8_t>(); }
     if (utf8) {
-      key_bytes_total = b->key_offsets[n];
+      in.key_bytes_total = b->key_offsets[n];
       KHIP_TRY(stage(a, a->st_koff, b->key_offsets, (n + 1) * 8));
-      KHIP_TRY(stage(a, a->st_kbytes, b->key_bytes, (size_t)std::max<int64_t>(key_bytes_total, 1)));
-      koff = a->st_koff.as<int64_t>();
-      kbytes = a->st_kbytes.as<uint8_t>();
+      KHIP_TRY(stage(a, a->st_kbytes, b->key_bytes, (size_t)std::max<int64_t>(in.key_bytes_total, 1)));
+      in.koff = a->st_koff.as<int64_t>();
+      in.kbytes = a->st_kbytes.as<uint8_t>();
     } else {
       KHIP_TRY(stage(a, a->st_keys, b->key_i64, n * 8));
-      keys = a->st_keys.as<int64_t>();
+      in.keys = a->st_keys.as<int64_t>();
     }
+    const size_t bm = (size_t)(n + 7) / 8;
     for (int c = 0; c < a->desc.n_cols; c++) {
       const size_t es = a->col_types[c] == KHIP_TYPE_INT32 ? 4 : 8;
       KHIP_TRY(stage(a, a->st_cols[c], b->col_data[c], n * es));
-      cols.data[c] = a->st_cols[c].p;
+      in.cols.data[c] = a->st_cols[c].p;
       const uint8_t* cv = b->col_valid ? b->col_valid[c] : nullptr;
       if (cv) {
         KHIP_TRY(stage(a, a->st_cval[c], cv, bm));
-        cols.valid[c] = a->st_cval[c].as<uint8_t>();
+        in.cols.valid[c] = a->st_cval[c].as<uint8_t>();
       }
     }
-  } else if (b->mem == KHIP_MEM_DEVICE) {
+  } else {
     for (int c = 0; c < a->desc.n_cols; c++) {
-      cols.data[c] = b->col_data[c];
-      cols.valid[c] = b->col_valid ? b->col_valid[c] : nullptr;
+      in.cols.data[c] = b->col_data[c];
+      in.cols.valid[c] = b->col_valid ? b->col_valid[c] : nullptr;
     }
     if (utf8)
-      KHIP_TRY_HIP(hipMemcpyAsync(&key_bytes_total, koff + n, 8, hipMemcpyDeviceToHost, a->stream));
-  } else {
-    return fail(KHIP_E_INVALID, "batch mem");
+      KHIP_TRY_HIP(hipMemcpyAsync(&in.key_bytes_total, in.koff + n, 8, hipMemcpyDeviceToHost, a->stream));
   }
-  *keys_o = keys;
-  *ts_o = ts;
-  *kv_o = kv;
-  *rv_o = rv;
-  *koff_o = koff;
-  *kbytes_o = kbytes;
-  *cols_o = cols;
-  *key_bytes_total_o = key_bytes_total;
+  in.hkeys = in.keys;
   return KHIP_OK;
+}
+
+// UTF8 GROUP BY keys → stable key ids (in.keys) through the handle's dictionary, with the key hashes
+// (in.hkeys) when want_hash: they only feed the slot hashing of the global-atomic table (the other
+// engines hash the ids).  timed: synchronise first (a device batch's key_bytes_total) and bracket the
+// map with the profile events 1 and 2; khip_agg_push_table has synchronised already and times nothing.
+static khip_status key_ids(khip_agg* a, BatchIn& in, bool want_hash, bool timed) {
+  if (timed) {
+    KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
+    ev_record(a, 1);
+  }
+  KHIP_TRY(a->kid.ensure(in.n * 8));
+  if (want_hash) KHIP_TRY(a->khash.ensure(in.n * 8));
+  KHIP_TRY(dict_map(a->dict, a->stream, in.koff, in.kbytes, in.key_bytes_total, in.kv, in.rv, in.ts, in.n,
+                    a->kid.as<int64_t>(), want_hash ? a->khash.as<int64_t>() : nullptr));
+  in.keys = a->kid.as<int64_t>();
+  in.hkeys = want_hash ? a->khash.as<int64_t>() : in.keys;
+  if (timed) ev_record(a, 2);
+  return KHIP_OK;
+}
+
+// A push's statistics from its counters tot[P_*] (null: an empty push, every count 0).  The table
+// aggregation fills neither dropped_null_row nor windows_late.
+static void put_stats(const khip_agg* a, int64_t rows_in, const int64_t* tot, bool table_source,
+                      khip_batch_stats* stats) {
+  if (!stats) return;
+  khip_batch_stats s{};
+  s.rows_in = rows_in;
+  if (tot) {
+    s.rows_accepted = tot[P_ACCEPTED];
+    s.dropped_null_key = tot[P_NULL_KEY];
+    if (!table_source) s.dropped_null_row = tot[P_NULL_ROW];
+    s.dropped_bad_ts = tot[P_BAD_TS];
+    s.windows_applied = tot[P_APPLIED];
+    if (!table_source) s.windows_late = tot[P_LATE];
+  }
+  s.stream_time = a->host_stream_time;
+  *stats = s;
+}
+
+// KHIP_FLAG_PROFILE, partitioned engine: a push's phase times from the events its last part_push /
+// part_push_rows left, its records and its one apply launch.  dict: the key dictionary's time too
+// (events 1-2 of key_ids).
+static void part_profile(khip_agg* a, int64_t n, bool dict) {
+  if (!a->profile) return;
+  a->times.stream_time_ms += ev_ms(a, 3, 4);
+  a->times.partition_ms += ev_ms(a, 4, 5);
+  a->times.apply_ms += ev_ms(a, 5, 6);
+  if (dict) a->times.dict_ms += ev_ms(a, 1, 2);
+  a->times.records += n;
+  a->times.apply_launches++;
+}
+
+// Retention, partitioned engine: drop expired windows from the closed store.  bounds: under
+// KHIP_TIME_PARTITION each row expires by its own task's bound (partition_bounds).
+static khip_status purge_expired(khip_agg* a, bool bounds) {
+  if (!a->windowed) return KHIP_OK;
+  HavingDev vis{};
+  vis.vis = 1;
+  vis.vis_from = visible_from(a);
+  if (vis.vis_from == INT64_MIN) return KHIP_OK;
+  if (bounds) KHIP_TRY(partition_bounds(a, vis));
+  return part_purge_closed(a, vis);
+}
+
+// The resolve kernels' argument for rows [base, base + rows) of the sequence: the handle's offset
+// aggregates and the push's (or slice's) user columns.
+static OffResolve off_query(const khip_agg* a, const ColPtrs& cols, int64_t base, int64_t rows) {
+  OffResolve q = a->offs;
+  for (int c = 0; c < a->desc.n_cols; c++) {
+    q.data[c] = cols.data[c];
+    q.valid[c] = cols.valid[c];
+  }
+  q.base = base;
+  q.rows = rows;
+  return q;
 }
 
 // KHIP_TIME_SUPPLIED with a close context: the handle's stream time becomes the GLOBAL one after the
@@ -1836,8 +1298,7 @@ khip_status khip_agg_push_shuffled(khip_agg* a, const khip_shuffle* sh, const ui
     return fail(KHIP_E_INVALID, "KHIP_TIME_SUPPLIED: the shuffle carries no stream time (KHIP_SHUFFLE_STREAM_TIME)");
   DeviceGuard g(a->device);
   if (n > 0 && n < (1LL << 31) && a->engine == 0 && a->desc.emit != KHIP_EMIT_FINAL) {
-    khip_batch_stats s{};
-    s.rows_in = n;
+    // (the pipeline's push: no SUPPLIED close context is consumed, no dictionary, no PARTITION domain)
     a->st_before = a->host_stream_time;
     a->chg_ready = false;
     a->lost.clear();
@@ -1846,27 +1307,9 @@ khip_status khip_agg_push_shuffled(khip_agg* a, const khip_shuffle* sh, const ui
     KHIP_TRY(part_push_rows(a, n, RowsIn{rows, rw, 0, 0}, kc, tot, &done, sup));
     if (done) {
       a->occ += tot[P_NEW];
-      if (a->profile) {
-        a->times.stream_time_ms += ev_ms(a, 3, 4);
-        a->times.partition_ms += ev_ms(a, 4, 5);
-        a->times.apply_ms += ev_ms(a, 5, 6);
-        a->times.records += n;
-        a->times.apply_launches++;
-      }
-      if (a->windowed) {  // retention: drop expired windows from the closed store
-        HavingDev vis{};
-        vis.vis = 1;
-        vis.vis_from = visible_from(a);
-        if (vis.vis_from != INT64_MIN) KHIP_TRY(part_purge_closed(a, vis));
-      }
-      s.rows_accepted = tot[P_ACCEPTED];
-      s.dropped_null_key = tot[P_NULL_KEY];
-      s.dropped_null_row = tot[P_NULL_ROW];
-      s.dropped_bad_ts = tot[P_BAD_TS];
-      s.windows_applied = tot[P_APPLIED];
-      s.windows_late = tot[P_LATE];
-      s.stream_time = a->host_stream_time;
-      if (stats) *stats = s;
+      part_profile(a, n, false);
+      KHIP_TRY(purge_expired(a, false));
+      put_stats(a, n, tot, false, stats);
       return KHIP_OK;
     }
   }
@@ -1925,22 +1368,13 @@ khip_status khip_agg_push_table(khip_agg* a, const khip_batch* b, const khip_tab
     if (src_utf8) KHIP_TRY(dict_init(T.dict, a->stream));
     T.key_type = src->key_type;
   }
-  khip_batch_stats s{};
-  s.rows_in = n;
   a->chg_ready = false;
   if (n == 0) {
-    s.stream_time = a->host_stream_time;
-    if (stats) *stats = s;
+    put_stats(a, 0, nullptr, true, stats);
     return KHIP_OK;
   }
-  const int64_t* keys;
-  const int64_t* ts;
-  const uint8_t *kv, *rv;
-  const int64_t* koff;
-  const uint8_t* kbytes;
-  ColPtrs cols{};
-  int64_t key_bytes_total = 0;
-  KHIP_TRY(resolve_batch(a, b, &keys, &ts, &kv, &rv, &koff, &kbytes, &cols, &key_bytes_total));
+  BatchIn in;
+  KHIP_TRY(resolve_batch(a, b, in));
   // the source PRIMARY KEYs on the device
   const int64_t* sk = src->key_i64;
   const int64_t* skoff = src->key_offsets;
@@ -1965,30 +1399,17 @@ khip_status khip_agg_push_table(khip_agg* a, const khip_batch* b, const khip_tab
   }
   KHIP_TRY_HIP(hipStreamSynchronize(a->stream));  // key byte totals of device batches
   // GROUP BY keys → ids (UTF8: the group dictionary; rows that cannot add to a group are skipped)
-  const int64_t* hkeys = keys;
-  if (utf8) {
-    KHIP_TRY(a->kid.ensure(n * 8));
-    KHIP_TRY(a->khash.ensure(n * 8));
-    KHIP_TRY(dict_map(a->dict, a->stream, koff, kbytes, key_bytes_total, kv, rv, ts, n, a->kid.as<int64_t>(),
-                      a->khash.as<int64_t>()));
-    keys = a->kid.as<int64_t>();
-    hkeys = a->khash.as<int64_t>();
-  }
+  if (utf8) KHIP_TRY(key_ids(a, in, true, false));
   if (src_utf8) {
     KHIP_TRY(T.sid.ensure(n * 8));
     KHIP_TRY(T.shash.ensure(n * 8));
-    KHIP_TRY(dict_map(T.dict, a->stream, skoff, skb, src_bytes, skv, nullptr, ts, n, T.sid.as<int64_t>(),
+    KHIP_TRY(dict_map(T.dict, a->stream, skoff, skb, src_bytes, skv, nullptr, in.ts, n, T.sid.as<int64_t>(),
                       T.shash.as<int64_t>()));
     sk = T.sid.as<int64_t>();
   }
   int64_t tot[NPART] = {0};
-  KHIP_TRY(tagg_push(a, n, keys, hkeys, kv, rv, ts, cols, sk, skv, tot));
-  s.rows_accepted = tot[P_ACCEPTED];
-  s.dropped_null_key = tot[P_NULL_KEY];
-  s.dropped_bad_ts = tot[P_BAD_TS];
-  s.windows_applied = tot[P_APPLIED];
-  s.stream_time = a->host_stream_time;
-  if (stats) *stats = s;
+  KHIP_TRY(tagg_push(a, n, in.keys, in.hkeys, in.kv, in.rv, in.ts, in.cols, sk, skv, tot));
+  put_stats(a, n, tot, true, stats);
   return KHIP_OK;
 }
 
@@ -1997,14 +1418,8 @@ khip_status khip_agg_push_table(khip_agg* a, const khip_batch* b, const khip_tab
 // closed store (a window can be updated and closed by the same push).
 static khip_status off_resolve_part(khip_agg* a, const ColPtrs& cols, int64_t base, int64_t m, int64_t closed0) {
   PartState& s = a->part;
-  OffResolve q = a->offs;
-  for (int c = 0; c < a->desc.n_cols; c++) {
-    q.data[c] = cols.data[c];
-    q.valid[c] = cols.valid[c];
-  }
-  q.base = base;
-  q.rows = m;
-  const bool lists = off_has_lists(a->offs);  // (an N form: the kernels' list code)
+  const OffResolve q = off_query(a, cols, base, m);
+  const bool lists = off_has_lists(q);  // (an N form: the kernels' list code)
   auto rpart = lists ? k_off_resolve_part<true> : k_off_resolve_part<false>;
   auto rrows = lists ? k_off_resolve_rows<true> : k_off_resolve_rows<false>;
   hipLaunchKernelGGL(rpart, dim3((unsigned)s.P), dim3(256), 0, a->stream, s.buf[0].as<uint64_t>(),
@@ -2019,8 +1434,9 @@ static khip_status off_resolve_part(khip_agg* a, const ColPtrs& cols, int64_t ba
   return KHIP_OK;
 }
 
-khip_status khip_agg_push(khip_agg* a, const khip_batch* b, khip_batch_stats* stats) {
-  clear_error();
+// ---- khip_agg_push: its stages, in the order they run
+
+static khip_status push_check(const khip_agg* a, const khip_batch* b) {
   if (!a || !b) return fail(KHIP_E_INVALID, "null argument");
   if (b->n_rows < 0 || b->n_cols < a->desc.n_cols) return fail(KHIP_E_INVALID, "batch shape");
   if (b->n_rows >= (1LL << 36)) return fail(KHIP_E_UNSUPPORTED, "batch larger than 2^36 rows");
@@ -2031,147 +1447,134 @@ khip_status khip_agg_push(khip_agg* a, const khip_batch* b, khip_batch_stats* st
     if (n > 0) return fail(KHIP_E_INVALID, "missing key or timestamp column");
   for (int c = 0; c < a->desc.n_cols; c++)
     if (n > 0 && (!b->col_data || !b->col_data[c])) return fail(KHIP_E_INVALID, "missing value column");
-  DeviceGuard g(a->device);
-  khip_batch_stats s{};
-  s.rows_in = n;
+  return KHIP_OK;
+}
+
+// The SUPPLIED close context (*sctx: this push consumes one), the emission state of the last push
+// forgotten, and the two empty batches, which end the push here (*done).
+static khip_status push_begin(khip_agg* a, int64_t n, bool* sctx, bool* done, khip_batch_stats* stats) {
   const bool supd = a->desc.time_domain == KHIP_TIME_SUPPLIED;
   if (supd && a->desc.emit == KHIP_EMIT_FINAL && !a->sup_set)
     return fail(KHIP_E_INVALID, "KHIP_TIME_SUPPLIED + EMIT FINAL: khip_agg_supplied_close before every push");
-  const bool sctx = supd && a->sup_set;
+  *sctx = supd && a->sup_set;
   a->sup_set = false;
-  a->st_before = sctx ? a->sup_before : a->host_stream_time;
+  a->st_before = *sctx ? a->sup_before : a->host_stream_time;
   a->chg_ready = false;
   a->lost.clear();
-  if (n == 0 && !sctx) {  // nothing changes, nothing closes
+  *done = n == 0;
+  if (n == 0 && !*sctx) {  // nothing changes, nothing closes
     a->chg_ready = true;
     a->chg_n = 0;
-    s.stream_time = a->host_stream_time;
-    if (stats) *stats = s;
+    put_stats(a, 0, nullptr, false, stats);
     return KHIP_OK;
   }
   if (n == 0) {  // SUPPLIED: nothing arrived here, but the GLOBAL stream time may close windows
     KHIP_TRY(supplied_advance(a));
     if (a->desc.emit == KHIP_EMIT_FINAL) a->lost = a->sup_lost;
     else a->chg_ready = true, a->chg_n = 0;
-    s.stream_time = a->host_stream_time;
-    if (stats) *stats = s;
+    put_stats(a, 0, nullptr, false, stats);
     return KHIP_OK;
   }
   if (a->changelog && n >= (1LL << 31)) return fail(KHIP_E_UNSUPPORTED, "changelog pushes above 2^31 rows");
-  const bool final_emit = a->desc.emit == KHIP_EMIT_FINAL;
-  // ---- device pointers (stage host batches)
-  const int64_t* keys;
-  const int64_t* ts;
-  const uint8_t *kv, *rv;
-  const int64_t* koff;
-  const uint8_t* kbytes;
-  ColPtrs cols{};
-  int64_t key_bytes_total = 0;
-  KHIP_TRY(resolve_batch(a, b, &keys, &ts, &kv, &rv, &koff, &kbytes, &cols, &key_bytes_total));
-  if (a->n_hidden) {  // offset aggregates: the hidden sequence columns (one iota, the arguments' validity)
-    KHIP_TRY(a->seqbuf.ensure((size_t)n * 8));
-    hipLaunchKernelGGL(k_off_iota, dim3(grid_for(n, 256, 4096)), dim3(256), 0, a->stream, a->seqbuf.as<int64_t>(), n,
-                       a->seq_base);
+  return KHIP_OK;
+}
+
+// Offset aggregates: the hidden sequence columns behind the user columns (one iota, the arguments'
+// validity).
+static khip_status push_hidden_cols(khip_agg* a, BatchIn& in) {
+  if (!a->n_hidden) return KHIP_OK;
+  const int64_t n = in.n;
+  KHIP_TRY(a->seqbuf.ensure((size_t)n * 8));
+  hipLaunchKernelGGL(k_off_iota, dim3(grid_for(n, 256, 4096)), dim3(256), 0, a->stream, a->seqbuf.as<int64_t>(), n,
+                     a->seq_base);
+  KHIP_TRY_HIP(hipGetLastError());
+  bool any_not = false;
+  for (int h = 0; h < a->n_hidden; h++) any_not = any_not || a->hid_not[h];
+  if (any_not) {  // EARLIEST's N forms: the complemented sequence
+    KHIP_TRY(a->nseqbuf.ensure((size_t)n * 8));
+    hipLaunchKernelGGL(k_off_iota_not, dim3(grid_for(n, 256, 4096)), dim3(256), 0, a->stream,
+                       a->nseqbuf.as<int64_t>(), n, a->seq_base);
     KHIP_TRY_HIP(hipGetLastError());
-    bool any_not = false;
-    for (int h = 0; h < a->n_hidden; h++) any_not = any_not || a->hid_not[h];
-    if (any_not) {  // EARLIEST's N forms: the complemented sequence
-      KHIP_TRY(a->nseqbuf.ensure((size_t)n * 8));
-      hipLaunchKernelGGL(k_off_iota_not, dim3(grid_for(n, 256, 4096)), dim3(256), 0, a->stream,
-                         a->nseqbuf.as<int64_t>(), n, a->seq_base);
-      KHIP_TRY_HIP(hipGetLastError());
-    }
-    for (int h = 0; h < a->n_hidden; h++) {
-      cols.data[a->desc.n_cols + h] = a->hid_not[h] ? a->nseqbuf.p : a->seqbuf.p;
-      cols.valid[a->desc.n_cols + h] = a->hid_src[h] >= 0 ? cols.valid[a->hid_src[h]] : nullptr;
-    }
   }
+  for (int h = 0; h < a->n_hidden; h++) {
+    in.cols.data[a->desc.n_cols + h] = a->hid_not[h] ? a->nseqbuf.p : a->seqbuf.p;
+    in.cols.valid[a->desc.n_cols + h] = a->hid_src[h] >= 0 ? in.cols.valid[a->hid_src[h]] : nullptr;
+  }
+  return KHIP_OK;
+}
+
+// What the batch's times decide before the engine runs: EMIT FINAL's lost windows in the TASK
+// domain, and the ABI 5 stream-time domains' column in.st_at, the stream time observed at every row
+// (SUPPLIED: the caller's; PARTITION: scanned per source partition, with its lost windows).
+static khip_status push_stream_time(khip_agg* a, const khip_batch* b, BatchIn& in, bool sctx) {
+  const int64_t n = in.n;
+  const bool final_emit = a->desc.emit == KHIP_EMIT_FINAL;
   const bool pdomain = a->desc.time_domain == KHIP_TIME_PARTITION;
   // (SESSION windows close sessions themselves: sess_push)
-  if (final_emit && !pdomain && !sctx && a->engine != 2) KHIP_TRY(emit_final_lost(a, ts, kv, rv, n, a->st_before, nullptr));
-  // ---- ABI 5 stream-time domains: the stream time observed at every row
-  const int64_t* st_at = nullptr;
-  const int32_t* part = nullptr;
+  if (final_emit && !pdomain && !sctx && a->engine != 2)
+    KHIP_TRY(emit_final_lost(a, in.ts, in.kv, in.rv, n, a->st_before));
   if (a->desc.time_domain == KHIP_TIME_SUPPLIED) {
     if (!b->stream_time) return fail(KHIP_E_INVALID, "KHIP_TIME_SUPPLIED: the batch has no stream_time column");
     if (b->mem == KHIP_MEM_HOST) {
       KHIP_TRY(stage(a, a->st_col, b->stream_time, n * 8));
-      st_at = a->st_col.as<int64_t>();
+      in.st_at = a->st_col.as<int64_t>();
     } else {
-      st_at = b->stream_time;
+      in.st_at = b->stream_time;
     }
-  } else if (a->desc.time_domain == KHIP_TIME_PARTITION) {
+  } else if (pdomain) {
     if (!b->partition) return fail(KHIP_E_INVALID, "KHIP_TIME_PARTITION: the batch has no partition column");
-    part = b->partition;
+    in.part = b->partition;
     if (b->mem == KHIP_MEM_HOST) {
       KHIP_TRY(stage(a, a->st_part, b->partition, n * 4));
-      part = a->st_part.as<int32_t>();
+      in.part = a->st_part.as<int32_t>();
     }
     KHIP_TRY(a->st_col.ensure((size_t)n * 8));
-    KHIP_TRY(stream_time_column(a, ts, kv, rv, part, n, -1, a->st_col.as<int64_t>(), nullptr));
-    st_at = a->st_col.as<int64_t>();
-    if (final_emit) KHIP_TRY(partition_lost(a, ts, kv, rv, part, st_at, n));
+    KHIP_TRY(stream_time_column(a, in.ts, in.kv, in.rv, in.part, n, -1, a->st_col.as<int64_t>(), nullptr));
+    in.st_at = a->st_col.as<int64_t>();
+    if (final_emit) KHIP_TRY(partition_lost(a, in.ts, in.kv, in.rv, in.part, in.st_at, n));
   }
-  // ---- UTF8 keys → stable key ids
-  const int64_t* hkeys = keys;
-  if (utf8) {
-    KHIP_TRY_HIP(hipStreamSynchronize(a->stream));  // key_bytes_total for device batches
-    ev_record(a, 1);
-    KHIP_TRY(a->kid.ensure(n * 8));
-    // the key hashes only feed the global-atomic engine's slot hashing (the others hash the ids)
-    const bool want_hash = a->engine == 1;
-    if (want_hash) KHIP_TRY(a->khash.ensure(n * 8));
-    KHIP_TRY(dict_map(a->dict, a->stream, koff, kbytes, key_bytes_total, kv, rv, ts, n, a->kid.as<int64_t>(),
-                      want_hash ? a->khash.as<int64_t>() : nullptr));
-    keys = a->kid.as<int64_t>();
-    hkeys = want_hash ? a->khash.as<int64_t>() : keys;
-    ev_record(a, 2);
+  return KHIP_OK;
+}
+
+// PARTITION domain, per-task retention / EMIT FINAL: every accepted key's partition (the tasks share
+// one table).  A batch that puts a key on a second partition is rejected before it changes the
+// handle's stream times: the partitions' stream times go back to their values before the batch (the
+// batch's new keys stay recorded with the partitions it named, as its dictionary entries stay).
+static khip_status push_key_partitions(khip_agg* a, const BatchIn& in) {
+  if (a->desc.time_domain != KHIP_TIME_PARTITION || !a->windowed) return KHIP_OK;
+  const khip_status ps = pmap_insert(a, in.keys, in.kv, in.rv, in.ts, in.part, in.n);
+  if (ps != KHIP_OK) std::swap(a->pst, a->pst2);
+  return ps;
+}
+
+// Partitioned engine: part_push in slices of < 2^31 records (multiple of 8: bitmaps stay byte
+// aligned), each followed by its offset aggregates' resolve.
+static khip_status part_push_slices(khip_agg* a, const BatchIn& in, int64_t* tot) {
+  const int64_t n = in.n, slice = 1LL << 31;
+  for (int64_t off = 0; off < n; off += slice) {
+    const int64_t m = std::min(slice, n - off);
+    ColPtrs cs = in.cols;
+    for (int c = 0; c < a->ap.n_cols; c++) {  // (the hidden sequence columns too: the base advances per slice)
+      cs.data[c] = (const char*)in.cols.data[c] + off * (a->ap.col_type[c] == KHIP_TYPE_INT32 ? 4 : 8);
+      if (cs.valid[c]) cs.valid[c] += off / 8;
+    }
+    const int64_t closed0 = a->part.closed_n;
+    KHIP_TRY(part_push(a, m, in.keys + off, in.ts + off, in.kv ? in.kv + off / 8 : nullptr,
+                       in.rv ? in.rv + off / 8 : nullptr, cs, tot, in.st_at ? in.st_at + off : nullptr));
+    // offset aggregates: the slice's winning sequence numbers become values, before the closed
+    // store is purged and before anything reads rows or changes
+    if (a->offs.n) KHIP_TRY(off_resolve_part(a, cs, a->seq_base + off, m, closed0));
   }
-  // per-task retention / EMIT FINAL: every accepted key's partition (the tasks share one table)
-  // A batch that puts a key on a second partition is rejected before it changes the handle's
-  // stream times: the partitions' stream times go back to their values before the batch (the
-  // batch's new keys stay recorded with the partitions it named, as its dictionary entries stay).
-  if (pdomain && a->windowed) {
-    const khip_status ps = pmap_insert(a, keys, kv, rv, ts, part, n);
-    if (ps != KHIP_OK) {
-      std::swap(a->pst, a->pst2);
-      return ps;
-    }
-  }
-  int64_t tot[NPART] = {0};
-  if (a->engine == 2) {
-    if (n >= (1LL << 31)) return fail(KHIP_E_UNSUPPORTED, "SESSION pushes above 2^31 rows");
-    // SUPPLIED with a close context: the GLOBAL stream time after the batch bounds the store's
-    // expiry (sess_push expires against the handle's stream time after the push)
-    if (sctx) KHIP_TRY(supplied_advance(a));
-    KHIP_TRY(sess_push(a, n, keys, ts, kv, rv, cols, tot, st_at));
-  } else if (a->engine == 0) {
-    // ---- partitioned engine, in slices of < 2^31 records (multiple of 8: bitmaps stay byte aligned)
-    const int64_t slice = 1LL << 31;
-    for (int64_t off = 0; off < n; off += slice) {
-      const int64_t m = std::min(slice, n - off);
-      ColPtrs cs = cols;
-      for (int c = 0; c < a->ap.n_cols; c++) {  // (the hidden sequence columns too: the base advances per slice)
-        cs.data[c] = (const char*)cols.data[c] + off * (a->ap.col_type[c] == KHIP_TYPE_INT32 ? 4 : 8);
-        if (cs.valid[c]) cs.valid[c] += off / 8;
-      }
-      const int64_t closed0 = a->part.closed_n;
-      KHIP_TRY(part_push(a, m, keys + off, ts + off, kv ? kv + off / 8 : nullptr, rv ? rv + off / 8 : nullptr, cs,
-                         tot, st_at ? st_at + off : nullptr));
-      // offset aggregates: the slice's winning sequence numbers become values, before the closed
-      // store is purged and before anything reads rows or changes
-      if (a->offs.n) KHIP_TRY(off_resolve_part(a, cs, a->seq_base + off, m, closed0));
-    }
-    a->occ += tot[P_NEW];
-    if (a->profile) {  // events of the last slice
-      a->times.stream_time_ms += ev_ms(a, 3, 4);
-      a->times.partition_ms += ev_ms(a, 4, 5);
-      a->times.apply_ms += ev_ms(a, 5, 6);
-      if (utf8) a->times.dict_ms += ev_ms(a, 1, 2);
-      a->times.records += n;
-      a->times.apply_launches++;
-    }
-  } else {
+  return KHIP_OK;
+}
+
+// Global-atomic engine (engine 1), the sibling of part_push / sess_push: the stream time before
+// each block, then apply → reduce → finalize passes, resumed after a table doubling while records
+// ran out of probes; the offset aggregates re-probe their groups in the final table.  Profile: the
+// records count on pass 0, an apply launch per pass.
+static khip_status atomic_push(khip_agg* a, const BatchIn& in, int64_t* tot) {
+  const int64_t n = in.n;
+  const bool utf8 = a->desc.key_type == KHIP_KEY_UTF8;
   // ---- scratch
   const int64_t nb = ceil_div(n, RPB);
   KHIP_TRY(a->blockmax.ensure(nb * 8));
@@ -2183,29 +1586,29 @@ khip_status khip_agg_push(khip_agg* a, const khip_batch* b, khip_batch_stats* st
     a->resume_n = n;
   }
   KHIP_TRY_HIP(hipMemsetAsync(a->counters.p, 0, 8 * NPART, a->stream));
-  // ---- stream time before each block (atomic engine)
+  // ---- stream time before each block
   ev_record(a, 0);
-  hipLaunchKernelGGL(k_blockmax, dim3(nb), dim3(BLOCK), 0, a->stream, ts, kv, rv, n, a->blockmax.as<int64_t>(),
-                     st_at);
+  hipLaunchKernelGGL(k_blockmax, dim3(nb), dim3(BLOCK), 0, a->stream, in.ts, in.kv, in.rv, n,
+                     a->blockmax.as<int64_t>(), in.st_at);
   hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, a->stream, a->blockmax.as<int64_t>(), nb,
                      a->blockprefix.as<int64_t>(), a->stream_time.as<int64_t>());
   KHIP_TRY_HIP(hipGetLastError());
   ev_record(a, 2);
   // ---- grow the group table ahead of time if the resident load is high
-  if (2 * a->occ > a->cap) KHIP_TRY(grow_table(a, a->cap * 4));
+  if (2 * a->occ > a->cap) KHIP_TRY(agg_grow_table(a, a->cap * 4));
   // ---- apply (+ resume passes after doubling on probe exhaustion)
   const int64_t occ0 = a->occ;
   double apply_ms = 0, fin_ms = 0;
   for (int pass = 0;; pass++) {
     ev_record(a, 3);
-    hipLaunchKernelGGL(k_apply, dim3(nb), dim3(BLOCK), 0, a->stream, a->ap, hkeys, keys, ts, kv, rv, cols,
-                       a->blockprefix.as<int64_t>(), n, a->table.as<uint64_t>(), (uint64_t)(a->cap - 1),
-                       a->resume.as<int32_t>(), a->partials.as<int64_t>(), pass > 0 ? 1 : 0, st_at);
+    hipLaunchKernelGGL(k_apply, dim3(nb), dim3(BLOCK), 0, a->stream, a->ap, in.hkeys, in.keys, in.ts, in.kv, in.rv,
+                       in.cols, a->blockprefix.as<int64_t>(), n, a->table.as<uint64_t>(), (uint64_t)(a->cap - 1),
+                       a->resume.as<int32_t>(), a->partials.as<int64_t>(), pass > 0 ? 1 : 0, in.st_at);
     ev_record(a, 4);
     hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, a->stream, a->partials.as<int64_t>(), nb, NPART,
                        a->counters.as<int64_t>());
     hipLaunchKernelGGL(k_finalize, dim3(grid_for(a->cap, 256)), dim3(256), 0, a->stream, a->table.as<uint64_t>(),
-                       a->cap, a->sw, keys, ts, a->windowed, a->desc.size_ms, a->desc.advance_ms);
+                       a->cap, a->sw, in.keys, in.ts, a->windowed, a->desc.size_ms, a->desc.advance_ms);
     KHIP_TRY_HIP(hipGetLastError());
     ev_record(a, 5);
     int64_t c[NPART];
@@ -2226,26 +1629,44 @@ khip_status khip_agg_push(khip_agg* a, const khip_batch* b, khip_batch_stats* st
     }
     if (failed == 0) break;
     if (pass > 40) return fail(KHIP_E_DEVICE, "aggregate table could not absorb the batch");
-    KHIP_TRY(grow_table(a, a->cap * 2));
+    KHIP_TRY(agg_grow_table(a, a->cap * 2));
   }
   a->times.apply_ms += apply_ms;
   a->times.finalize_ms += fin_ms;
   if (a->offs.n) {  // offset aggregates: every record re-probes its groups (the table is final now)
-    OffResolve q = a->offs;
-    for (int c = 0; c < a->desc.n_cols; c++) {
-      q.data[c] = cols.data[c];
-      q.valid[c] = cols.valid[c];
-    }
-    q.base = a->seq_base;
-    q.rows = n;
+    const OffResolve q = off_query(a, in.cols, a->seq_base, n);
     auto probe = off_has_lists(q) ? k_off_resolve_probe<true> : k_off_resolve_probe<false>;
-    hipLaunchKernelGGL(probe, dim3(grid_for(n, 256)), dim3(256), 0, a->stream, a->ap, hkeys, keys, ts,
-                       kv, rv, n, a->table.as<uint64_t>(), (uint64_t)(a->cap - 1), q);
+    hipLaunchKernelGGL(probe, dim3(grid_for(n, 256)), dim3(256), 0, a->stream, a->ap, in.hkeys, in.keys, in.ts,
+                       in.kv, in.rv, n, a->table.as<uint64_t>(), (uint64_t)(a->cap - 1), q);
     KHIP_TRY_HIP(hipGetLastError());
     KHIP_TRY_HIP(hipStreamSynchronize(a->stream));  // (a host batch's staging buffers are reused by the next push)
   }
+  return KHIP_OK;
+}
+
+// The batch into the handle's engine; tot[P_*]: the push's counters.
+static khip_status push_engine(khip_agg* a, const BatchIn& in, bool sctx, int64_t* tot) {
+  if (a->engine == 2) {
+    if (in.n >= (1LL << 31)) return fail(KHIP_E_UNSUPPORTED, "SESSION pushes above 2^31 rows");
+    // SUPPLIED with a close context: the GLOBAL stream time after the batch bounds the store's
+    // expiry (sess_push expires against the handle's stream time after the push)
+    if (sctx) KHIP_TRY(supplied_advance(a));
+    return sess_push(a, in.n, in.keys, in.ts, in.kv, in.rv, in.cols, tot, in.st_at);
   }
-  a->seq_base += n;
+  if (a->engine == 1) return atomic_push(a, in, tot);
+  KHIP_TRY(part_push_slices(a, in, tot));
+  a->occ += tot[P_NEW];
+  part_profile(a, in.n, a->desc.key_type == KHIP_KEY_UTF8);  // (once per push, from the last slice's events)
+  return KHIP_OK;
+}
+
+// The end of a push: the handle's stream time after the batch in its domain, EMIT FINAL's lost
+// windows, the retention purge of the closed store, the statistics.
+static khip_status push_finish(khip_agg* a, const BatchIn& in, bool sctx, const int64_t* tot,
+                               khip_batch_stats* stats) {
+  const bool final_emit = a->desc.emit == KHIP_EMIT_FINAL;
+  const bool pdomain = a->desc.time_domain == KHIP_TIME_PARTITION;
+  a->seq_base += in.n;
   if (a->engine == 1) {  // the other engines brought it back with their end-of-push counters
     KHIP_TRY_HIP(hipMemcpyAsync(&a->host_stream_time, a->stream_time.p, 8, hipMemcpyDeviceToHost, a->stream));
     KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
@@ -2254,25 +1675,30 @@ khip_status khip_agg_push(khip_agg* a, const khip_batch* b, khip_batch_stats* st
   if (pdomain) KHIP_TRY(stream_time_partition_min(a));
   if (sctx) KHIP_TRY(supplied_advance(a));  // one task over the whole stream: the GLOBAL stream time
   if (final_emit && sctx) a->lost = a->sup_lost;
-  else if (final_emit && a->engine != 2) KHIP_TRY(pdomain ? partition_lost_finish(a) : finish_lost(a, ts, kv, rv, n));
-  if (a->engine == 0 && a->windowed) {  // retention: drop expired windows from the closed store
-    HavingDev vis{};
-    vis.vis = 1;
-    vis.vis_from = visible_from(a);
-    if (vis.vis_from != INT64_MIN) {
-      KHIP_TRY(partition_bounds(a, vis));  // PARTITION: each row by its own task's bound
-      KHIP_TRY(part_purge_closed(a, vis));
-    }
-  }
-  s.rows_accepted = tot[P_ACCEPTED];
-  s.dropped_null_key = tot[P_NULL_KEY];
-  s.dropped_null_row = tot[P_NULL_ROW];
-  s.dropped_bad_ts = tot[P_BAD_TS];
-  s.windows_applied = tot[P_APPLIED];
-  s.windows_late = tot[P_LATE];
-  s.stream_time = a->host_stream_time;
-  if (stats) *stats = s;
+  else if (final_emit && a->engine != 2)
+    KHIP_TRY(pdomain ? partition_lost_finish(a) : finish_lost_seed(a, in.ts, in.kv, in.rv, in.n, a->st_before));
+  if (a->engine == 0) KHIP_TRY(purge_expired(a, true));  // (PARTITION: each row by its own task's bound)
+  put_stats(a, in.n, tot, false, stats);
   return KHIP_OK;
+}
+
+khip_status khip_agg_push(khip_agg* a, const khip_batch* b, khip_batch_stats* stats) {
+  clear_error();
+  KHIP_TRY(push_check(a, b));
+  DeviceGuard g(a->device);
+  bool sctx = false, done = false;
+  KHIP_TRY(push_begin(a, b->n_rows, &sctx, &done, stats));
+  if (done) return KHIP_OK;
+  BatchIn in;
+  KHIP_TRY(resolve_batch(a, b, in));  // device pointers (host batches staged)
+  KHIP_TRY(push_hidden_cols(a, in));
+  KHIP_TRY(push_stream_time(a, b, in, sctx));
+  // UTF8 keys → stable key ids; their hashes only for the global-atomic engine's slot hashing
+  if (a->desc.key_type == KHIP_KEY_UTF8) KHIP_TRY(key_ids(a, in, a->engine == 1, true));
+  KHIP_TRY(push_key_partitions(a, in));
+  int64_t tot[NPART] = {0};
+  KHIP_TRY(push_engine(a, in, sctx, tot));
+  return push_finish(a, in, sctx, tot, stats);
 }
 
 khip_status khip_stream_time_scan(khip_agg* a, const khip_batch* b, int64_t seed, int64_t* out, int64_t* out_max) {
@@ -2283,23 +1709,16 @@ khip_status khip_stream_time_scan(khip_agg* a, const khip_batch* b, int64_t seed
   const int64_t n = b->n_rows;
   *out_max = seed < -1 ? -1 : seed;
   if (n == 0) return KHIP_OK;
-  const int64_t* ts = b->ts;
-  const uint8_t *kv = b->key_valid, *rv = b->row_valid;
+  BatchIn in;
+  KHIP_TRY(stage_ts_valid(a, b, in));
   int64_t* dst = out;
-  const size_t bm = (size_t)(n + 7) / 8;
   if (b->mem == KHIP_MEM_HOST) {
-    KHIP_TRY(stage(a, a->st_ts, b->ts, n * 8));
-    ts = a->st_ts.as<int64_t>();
-    if (kv) { KHIP_TRY(stage(a, a->st_kv, kv, bm)); kv = a->st_kv.as<uint8_t>(); }
-    if (rv) { KHIP_TRY(stage(a, a->st_rv, rv, bm)); rv = a->st_rv.as<uint8_t>(); }
     KHIP_TRY(a->st_col.ensure((size_t)n * 8));
     dst = a->st_col.as<int64_t>();
-  } else if (b->mem != KHIP_MEM_DEVICE) {
-    return fail(KHIP_E_INVALID, "batch mem");
   }
   KHIP_TRY(a->st_seen.ensure(8));
   int64_t* last = a->st_seen.as<int64_t>();
-  KHIP_TRY(stream_time_column(a, ts, kv, rv, nullptr, n, seed < -1 ? -1 : seed, dst, last));
+  KHIP_TRY(stream_time_column(a, in.ts, in.kv, in.rv, nullptr, n, seed < -1 ? -1 : seed, dst, last));
   if (b->mem == KHIP_MEM_HOST) KHIP_TRY_HIP(hipMemcpyAsync(out, dst, (size_t)n * 8, hipMemcpyDeviceToHost, a->stream));
   KHIP_TRY_HIP(hipMemcpyAsync(out_max, last, 8, hipMemcpyDeviceToHost, a->stream));
   KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
@@ -2317,22 +1736,13 @@ khip_status khip_agg_lost_windows(khip_agg* a, const khip_batch* b, int64_t seed
   const int64_t n = b->n_rows;
   *n_ranges = 0;
   if (n == 0) return KHIP_OK;
-  const int64_t* ts = b->ts;
-  const uint8_t *kv = b->key_valid, *rv = b->row_valid;
-  const size_t bm = (size_t)(n + 7) / 8;
-  if (b->mem == KHIP_MEM_HOST) {
-    KHIP_TRY(stage(a, a->st_ts, b->ts, n * 8));
-    ts = a->st_ts.as<int64_t>();
-    if (kv) { KHIP_TRY(stage(a, a->st_kv, kv, bm)); kv = a->st_kv.as<uint8_t>(); }
-    if (rv) { KHIP_TRY(stage(a, a->st_rv, rv, bm)); rv = a->st_rv.as<uint8_t>(); }
-  } else if (b->mem != KHIP_MEM_DEVICE) {
-    return fail(KHIP_E_INVALID, "batch mem");
-  }
+  BatchIn in;
+  KHIP_TRY(stage_ts_valid(a, b, in));
   const int64_t sd = seed < -1 ? -1 : seed;
-  KHIP_TRY(emit_final_lost(a, ts, kv, rv, n, sd, nullptr));
+  KHIP_TRY(emit_final_lost(a, in.ts, in.kv, in.rv, n, sd));
   KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
   const std::vector<int64_t> keep = a->lost;  // (the handle's own last push)
-  KHIP_TRY(finish_lost_seed(a, ts, kv, rv, n, sd));
+  KHIP_TRY(finish_lost_seed(a, in.ts, in.kv, in.rv, n, sd));
   std::vector<int64_t> got;
   got.swap(a->lost);
   a->lost = keep;

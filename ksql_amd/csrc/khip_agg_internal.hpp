@@ -880,8 +880,9 @@ __global__ void k_finalize(uint64_t* __restrict__ table, int64_t cap, int sw, co
                            const int64_t* __restrict__ ts, int windowed, int64_t size, int64_t adv);
 // the first visible window start after the last push (INT64_MIN: nothing expired)
 int64_t visible_from(const khip_agg* a);
+// EMIT FINAL: launch the scan for the window starts a batch loses, seeded with the stream time before it
 khip_status emit_final_lost(khip_agg* a, const int64_t* ts, const uint8_t* kv, const uint8_t* rv, int64_t n,
-                            int64_t tile, const int64_t* tile_prefix);
+                            int64_t seed_st);
 // khip_stream_time.hip: the per-row stream time column (one seeded segment, or the partition runs
 // of `part` seeded with / updating a->pst), and the PARTITION domain's handle stream time
 khip_status stream_time_column(khip_agg* a, const int64_t* ts, const uint8_t* kv, const uint8_t* rv,

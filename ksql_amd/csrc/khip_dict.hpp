@@ -10,7 +10,7 @@
 //                        | resident:    bit62 | fp22 << 40 | id / 8
 //   arena entry at id o (8-aligned): [u64 hash][i64 len][bytes, padded to 8]
 // A map: k_dict_probe (claims, in-place compares, pending rows) → k_dict_commit (per claim) →
-// k_dict_resolve (per pending row); kernels in khip_agg.hip.
+// k_dict_resolve (per pending row); kernels and host side in khip_dict.hip.
 //
 // Inline keys: a key of 0..17 ASCII decimal digits ('0'-'9': card, account and phone numbers,
 // numeric ids kept as VARCHAR) has an exact 64-bit form and never enters the dictionary — its id

@@ -258,4 +258,10 @@ inline int64_t next_pow2(int64_t v) {
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Blocks for `work` items at `per_block` each: at least one, at most cap_blocks (grid-stride kernels).
+inline int grid_for(int64_t work, int per_block, int cap_blocks = 2048 * 8) {
+  const int64_t g = ceil_div(work > 1 ? work : 1, per_block);
+  return (int)(g < cap_blocks ? g : cap_blocks);
+}
+
 }  // namespace khip

@@ -126,7 +126,7 @@ def test_c1_utf8_keys(prod, orc):
 def test_c1_utf8_dictionary_growth(prod, orc):
     """The key dictionary is sized from the keys the last map added (twice that, at least n / 16),
     not from the batch size: a push bringing far more new keys than that fails its probes and is
-    mapped again into a larger table (khip_agg.hip dict_map); a reset gives back a table sized by
+    mapped again into a larger table (khip_dict.hip dict_map); a reset gives back a table sized by
     the first map's every-row estimate.  Rounds (a reset after each): [100 keys] (the reset shrinks
     the table), [100 keys, 150K new keys] (the second push is mapped again twice), the same again."""
     rng = np.random.default_rng(15)

@@ -167,6 +167,40 @@ typedef int32_t khip_status;
  * passed to snapshot / get / count_rows), and an aggregate list past the 29 state words of a row. */
 #define KHIP_AGG_STDDEV_SAMP 10
 #define KHIP_AGG_STDDEV_SAMPLE 11
+/* CORRELATION(x, y), x and y both INTEGER or both BIGINT: the Pearson correlation coefficient,
+ * function/udaf/correlation/CorrelationUdaf.java:48-67 (factories), :86-102 (aggregate), :104-113
+ * (merge), :115-134 (map), :136-152 (undo).  arg_col is x; y is OR-ed into the kind with
+ * KHIP_AGG_ARG2(col) (the bits of KHIP_AGG_K: y = column 0 is all-zero bits and valid; x == y is
+ * allowed).  A record counts when x and y are both non-null (aggregate :88-90).  The result is a
+ * DOUBLE, never SQL NULL: the canonical quiet NaN (0x7FF8000000000000) for a group with fewer than
+ * two pairs and whenever x or y is constant over the group's pairs, the reference's 0.0 / 0.0.
+ *
+ * The reference folds five running sums in double arithmetic, in arrival order; here a group keeps
+ * exact integer state (the pair count n, Σx, Σy, Σx², Σy², and the signed Σxy, over 64-bit words that
+ * only ever take commutative adds) and the result is decoded on the host, csrc/khip_correlation.hpp:
+ *   N = n Σxy - Σx Σy,  DX = n Σx² - (Σx)²,  DY = n Σy² - (Σy)²     exact integers
+ *   r = RN(N) / sqrt(RN(DX) * RN(DY))        RN: one round-half-even to a double; then map's own
+ *                                            three operations in its order (:127-133)
+ * Wherever every quantity the reference forms (its sums, count * sum, the products in map) stays
+ * below 2^53 in magnitude, r is bit-identical to the reference.  Everywhere else r is within
+ * 5 * 2^-53 relative of the true coefficient, where the reference's one-pass fold has no bound
+ * (INTEGRATION.md).  It does not depend on record order, engine, retries or how the stream is cut
+ * into pushes.  The state is exact for up to 2^32 - 1 pairs per group; beyond that the result is
+ * unspecified (nothing faults).
+ * State words: 9 (INT) or 17 (BIGINT): n; Σx, Σy (1 / 2 words each); Σx², Σy², Σxy (2 / 4 limb words
+ * each).  None is shared with COUNT / SUM / AVG / STDDEV of x or y, which count a record when that
+ * one column is non-null.  An identical (x, y) spec adds no words; CORRELATION(y, x) shares all the
+ * words of CORRELATION(x, y); CORRELATION(x, x) keeps 6 / 11.
+ * A TableUdaf: allowed with KHIP_FLAG_TABLE_SOURCE (undo = word-wise subtraction), with every
+ * window kind but SESSION, both engines, every time domain, EMIT CHANGES / FINAL, through
+ * khip_agg_push_shuffled, beside any other aggregate, several times in one query.
+ * KHIP_E_INVALID: y out of range, KHIP_AGG_KEEP_NULLS on this kind.
+ * KHIP_E_UNSUPPORTED: a DOUBLE argument (the one-pass formula cancels: no order-free state
+ * reproduces the reference's fold within a data-independent bound), mixed INT / BIGINT (cast one),
+ * SESSION windows, a HAVING on the CORRELATION aggregate itself (in the descriptor or passed to
+ * snapshot / get / count_rows), and an aggregate list past the 29 state words of a row. */
+#define KHIP_AGG_CORRELATION 12
+#define KHIP_AGG_ARG2(col) ((int32_t)(col) << 16)
 
 /* Where a batch's column pointers live. */
 #define KHIP_MEM_HOST 0

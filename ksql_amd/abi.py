@@ -31,7 +31,13 @@ AGG_KEEP_NULLS = 0x100  # KHIP_AGG_KEEP_NULLS: ignoreNulls = false, OR-ed into t
 AGG = {"COUNT_STAR": 0, "COUNT": 1, "SUM": 2, "MIN": 3, "MAX": 4, "AVG": 5,
        "LATEST_BY_OFFSET": 6, "EARLIEST_BY_OFFSET": 7,
        "LATEST_BY_OFFSET_NULLS": 6 | AGG_KEEP_NULLS, "EARLIEST_BY_OFFSET_NULLS": 7 | AGG_KEEP_NULLS,
-       "TOPK": 8, "TOPKDISTINCT": 9, "STDDEV_SAMP": 10, "STDDEV_SAMPLE": 11}
+       "TOPK": 8, "TOPKDISTINCT": 9, "STDDEV_SAMP": 10, "STDDEV_SAMPLE": 11, "CORRELATION": 12}
+
+
+def AGG_ARG2(col):
+    """KHIP_AGG_ARG2(col): CORRELATION's second argument column y, OR-ed into the aggregate kind (the
+    bits of AGG_K: make_agg_desc takes ("CORRELATION", x, y))."""
+    return int(col) << 16
 
 
 def AGG_K(k):
@@ -388,7 +394,8 @@ def make_agg_desc(window_kind="NONE", key_type="INT64", size_ms=0, advance_ms=0,
     """having: the query's HAVING ({"agg", "op", "value"}), maintained by the library (ABI 2).
     time_domain / n_partitions: the stream-time domain (ABI 5; include/ksqldb_hip.h KHIP_TIME_*).
     aggs: (kind, column) per aggregate; TOPK / TOPKDISTINCT take their k as a third element,
-    ("TOPK", column, k), and so do the N forms of the offset aggregates, ("LATEST_BY_OFFSET", column, N)."""
+    ("TOPK", column, k), and so do the N forms of the offset aggregates, ("LATEST_BY_OFFSET", column, N);
+    CORRELATION takes its second column there, ("CORRELATION", x, y)."""
     ct = (i32 * max(len(col_types), 1))(*[TYPE[t] if isinstance(t, str) else t for t in col_types])
     sp = (AggSpec * max(len(aggs), 1))(*[AggSpec((AGG[a[0]] if isinstance(a[0], str) else a[0]) |
                                                  (AGG_K(a[2]) if len(a) > 2 else 0), a[1]) for a in aggs])
@@ -443,6 +450,8 @@ def result_types(desc):
         if k in (AGG["COUNT_STAR"], AGG["COUNT"]):
             out.append(TYPE["INT64"])
         elif k in (AGG["AVG"], AGG["STDDEV_SAMP"], AGG["STDDEV_SAMPLE"]):
+            out.append(TYPE["DOUBLE"])
+        elif k & 0xFFFF == AGG["CORRELATION"]:  # (its second column is in the upper bits)
             out.append(TYPE["DOUBLE"])
         else:  # SUM / MIN / MAX, LATEST / EARLIEST_BY_OFFSET (scalar and N forms, with or without AGG_KEEP_NULLS),
             # TOPK / TOPKDISTINCT

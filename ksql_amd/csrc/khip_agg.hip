@@ -35,6 +35,7 @@
 
 #include "khip_agg_internal.hpp"
 #include "khip_variance.hpp"
+#include "khip_correlation.hpp"
 
 namespace khip {
 
@@ -244,9 +245,18 @@ __device__ __forceinline__ int upsert_apply(const ApplyParams& p, uint64_t* __re
           }
           default:  // OP_ADD_HI32 / OP_ADD_SQ (STDDEV: x >> 32 / a limb of x², khip_variance.hpp); here, so
                     // that the dispatch of the kinds above stays what it was
-            if (op.kind == OP_ADD_HI32 || op.kind == OP_ADD_SQ)
+            if (op.kind == OP_ADD_HI32 || op.kind == OP_ADD_SQ) {
               __hip_atomic_fetch_add((uint64_t*)w, var_addend(op, load_col_raw(cols, ty, op.col, row)),
                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            } else if (op_is_pair(op)) {
+              // CORRELATION (khip_correlation.hpp): only a record with both arguments non-null counts
+              const int c2 = op_col2(op);
+              if (!bit_get(cols.valid[c2], row)) break;
+              __hip_atomic_fetch_add((uint64_t*)w,
+                                     pair_addend(op, load_col_raw(cols, ty, op.col, row),
+                                                 load_col_raw(cols, p.col_type[c2], c2, row)),
+                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
             break;
         }
       }
@@ -572,6 +582,7 @@ static inline bool agg_is_var(int32_t kind) {
   const int b = agg_base_kind(kind);
   return b == KHIP_AGG_STDDEV_SAMP || b == KHIP_AGG_STDDEV_SAMPLE;
 }
+static inline bool agg_is_pair(int32_t kind) { return agg_base_kind(kind) == KHIP_AGG_CORRELATION; }
 static inline bool off_has_lists(const OffResolve& q) {
   for (int k = 0; k < q.n; k++)
     if (q.a[k].n) return true;
@@ -639,6 +650,7 @@ static khip_status plan_state(khip_agg* a) {
       if (w_star < 0) w_star = word++;
       continue;
     }
+    if (agg_is_pair(s.kind)) continue;  // (its own words: below)
     const int c = s.arg_col;
     if (agg_is_topk(s.kind)) {  // TOPK's length is min(the column's non-null count, k); its slots: below
       if (s.kind == KHIP_AGG_TOPK && w_cnt[c] < 0) w_cnt[c] = word++;
@@ -658,6 +670,39 @@ static khip_status plan_state(khip_agg* a) {
     }
     if (s.kind == KHIP_AGG_MIN && w_min[c] < 0) w_min[c] = word++;
     if (s.kind == KHIP_AGG_MAX && w_max[c] < 0) w_max[c] = word++;
+  }
+  // CORRELATION(x, y) (khip_correlation.hpp): words that apply only when x and y are both non-null, so
+  // none is shared with COUNT / SUM / STDDEV of either column.  A run of consecutive words per
+  // (quantity, column, gate column); the pair count and Σxy are keyed by the unordered pair.  So an
+  // identical spec adds no word, CORRELATION(y, x) shares all of CORRELATION(x, y)'s, and
+  // CORRELATION(x, x) has one Σx run and one Σx² run.
+  struct PairRun { int kind, col, col2, word, limbs; };
+  std::vector<PairRun> pruns;
+  a->out_pair.assign(d.n_aggs, khip_agg::PairWords{});
+  a->has_pair = false;
+  for (int i = 0; i < d.n_aggs; i++) {
+    const khip_agg_spec& s = a->aggs[i];
+    if (!agg_is_pair(s.kind)) continue;
+    a->has_pair = true;
+    const int x = s.arg_col, y = a->agg_k[i];
+    const bool big = a->col_types[x] == KHIP_TYPE_INT64;
+    auto run = [&](int kind, int col, int col2, int limbs) {
+      for (const PairRun& r : pruns)
+        if (r.kind == kind && r.col == col && r.col2 == col2) return r.word;
+      if (word + limbs > 32) return -1;
+      pruns.push_back(PairRun{kind, col, col2, word, limbs});
+      word += limbs;
+      return pruns.back().word;
+    };
+    khip_agg::PairWords& w = a->out_pair[i];
+    w.w_n = run(OP_PAIR_N, std::min(x, y), std::max(x, y), 1);
+    w.w_sx = run(OP_PAIR_SUM, x, y, big ? 2 : 1);
+    w.w_sy = run(OP_PAIR_SUM, y, x, big ? 2 : 1);
+    w.w_sxx = run(OP_PAIR_SQ, x, y, big ? 4 : 2);
+    w.w_syy = run(OP_PAIR_SQ, y, x, big ? 4 : 2);
+    w.w_sxy = run(OP_PAIR_XY, std::min(x, y), std::max(x, y), big ? 4 : 2);
+    if (w.w_n < 0 || w.w_sx < 0 || w.w_sy < 0 || w.w_sxx < 0 || w.w_syy < 0 || w.w_sxy < 0)
+      return fail(KHIP_E_UNSUPPORTED, "too many aggregate state words (max 29)");
   }
   for (int i = 0; i < d.n_aggs; i++) {  // latest = MAX(seq), earliest = MIN(seq); no non-null count:
     if (off_hid[i] < 0) continue;       // the initial value itself says "no record yet"
@@ -738,6 +783,10 @@ static khip_status plan_state(khip_agg* a) {
     if (w_min[c] >= 0) add(OP_MIN, c, w_min[c]);
     if (w_max[c] >= 0) add(OP_MAX, c, w_max[c]);
   }
+  for (const PairRun& r : pruns)  // (op_word / op_limb / op_col2 / op_big)
+    for (int j = 0; j < r.limbs; j++)
+      add((int8_t)r.kind, r.col,
+          (r.word + j) | (j << 8) | (r.col2 << 11) | ((p.col_type[r.col] == KHIP_TYPE_INT64 ? 1 : 0) << 14));
   for (const TopkSpan& sp : spans)  // (op_word / op_slots)
     add(sp.kind == KHIP_AGG_TOPK ? OP_TOPK : OP_TOPK_DISTINCT, sp.col, sp.word | (sp.k << 8));
   p.n_ops = n;
@@ -758,7 +807,7 @@ static khip_status plan_state(khip_agg* a) {
     AggOut o{};
     o.kind = agg_base_kind(s.kind);
     o.type = s.kind == KHIP_AGG_COUNT_STAR ? KHIP_TYPE_INT64 : a->col_types[s.arg_col];
-    o.w_cnt = s.kind == KHIP_AGG_COUNT_STAR ? -1 : (agg_is_offset(s.kind) ? -1 : w_cnt[s.arg_col]);
+    o.w_cnt = s.kind == KHIP_AGG_COUNT_STAR ? -1 : (agg_is_offset(s.kind) || agg_is_pair(s.kind) ? -1 : w_cnt[s.arg_col]);
     switch (o.kind) {
       case KHIP_AGG_COUNT_STAR: o.w_val = w_star; break;
       case KHIP_AGG_COUNT: o.w_val = w_cnt[s.arg_col]; break;
@@ -770,6 +819,9 @@ static khip_status plan_state(khip_agg* a) {
         a->out_var[i].w_hi = w_hi[s.arg_col];
         a->out_var[i].w_sq = w_sq[s.arg_col];
         a->has_var = true;
+        break;
+      case KHIP_AGG_CORRELATION:  // (decoded by emit_snapshot: correlation_result over out_pair[i])
+        o.w_val = a->out_pair[i].w_n;
         break;
       case KHIP_AGG_MIN: o.w_val = w_min[s.arg_col]; break;
       case KHIP_AGG_MAX: o.w_val = w_max[s.arg_col]; break;
@@ -903,7 +955,7 @@ khip_status khip_agg_result_type(const khip_agg_desc* d, int32_t i, int32_t* out
   if (!d || !out || i < 0 || i >= d->n_aggs) return fail(KHIP_E_INVALID, "bad aggregate index");
   const khip_agg_spec& s = d->aggs[i];
   if (s.kind == KHIP_AGG_COUNT_STAR || s.kind == KHIP_AGG_COUNT) *out = KHIP_TYPE_INT64;
-  else if (s.kind == KHIP_AGG_AVG || agg_is_var(s.kind)) *out = KHIP_TYPE_DOUBLE;
+  else if (s.kind == KHIP_AGG_AVG || agg_is_var(s.kind) || agg_is_pair(s.kind)) *out = KHIP_TYPE_DOUBLE;
   else *out = d->col_types[s.arg_col];  // (TOPK / TOPKDISTINCT: the element type)
   return KHIP_OK;
 }
@@ -937,12 +989,15 @@ khip_status khip_agg_create(const khip_agg_desc* desc, khip_agg** out) {
   for (int i = 0; i < d.n_aggs; i++) {
     const khip_agg_spec& s = d.aggs[i];
     const int bk = agg_base_kind(s.kind);
-    if (bk < KHIP_AGG_COUNT_STAR || bk > KHIP_AGG_STDDEV_SAMPLE) return fail(KHIP_E_INVALID, "aggregate kind");
+    if (bk < KHIP_AGG_COUNT_STAR || bk > KHIP_AGG_CORRELATION) return fail(KHIP_E_INVALID, "aggregate kind");
     if ((s.kind & KHIP_AGG_KEEP_NULLS) && !agg_is_offset(s.kind))
       return fail(KHIP_E_INVALID, "KHIP_AGG_KEEP_NULLS on an aggregate other than LATEST / EARLIEST_BY_OFFSET");
     if (agg_is_offset(s.kind)) {  // no k bits: the scalar form; N >= 1: the N form (an ARRAY, also for N = 1)
       if (agg_k_bits(s.kind) < 0)
         return fail(KHIP_E_INVALID, "LATEST / EARLIEST_BY_OFFSET: N (KHIP_AGG_K) must be at least 1");
+    } else if (agg_is_pair(s.kind)) {  // KHIP_AGG_ARG2: the second argument column in the k bits
+      if (agg_k_bits(s.kind) < 0 || agg_k_bits(s.kind) >= d.n_cols)
+        return fail(KHIP_E_INVALID, "CORRELATION: second argument column (KHIP_AGG_ARG2)");
     } else if (agg_is_topk(s.kind) ? agg_k_bits(s.kind) < 1 : agg_k_bits(s.kind) != 0)
       return fail(KHIP_E_INVALID, agg_is_topk(s.kind)
                                       ? "TOPK / TOPKDISTINCT: k (KHIP_AGG_K) must be at least 1"
@@ -963,6 +1018,18 @@ khip_status khip_agg_create(const khip_agg_desc* desc, khip_agg** out) {
       if (d.has_having && d.having.agg_index == i)
         return fail(KHIP_E_UNSUPPORTED, "HAVING on a STDDEV_SAMP / STDDEV_SAMPLE aggregate");
     }
+  }
+  for (int i = 0; i < d.n_aggs; i++) {
+    const khip_agg_spec& s = d.aggs[i];
+    if (!agg_is_pair(s.kind)) continue;
+    const int tx = d.col_types[s.arg_col], ty = d.col_types[agg_k_bits(s.kind)];
+    // a DOUBLE argument: the reference's one-pass formula cancels (CorrelationUdaf.java:127-133), so
+    // no order-free state reproduces its fold within a bound that does not depend on the data
+    if (tx == KHIP_TYPE_DOUBLE || ty == KHIP_TYPE_DOUBLE)
+      return fail(KHIP_E_UNSUPPORTED, "CORRELATION of a DOUBLE column");
+    if (tx != ty) return fail(KHIP_E_UNSUPPORTED, "CORRELATION of an INT and a BIGINT column (cast one)");
+    if (d.window_kind == KHIP_WINDOW_SESSION) return fail(KHIP_E_UNSUPPORTED, "CORRELATION with SESSION windows");
+    if (d.has_having && d.having.agg_index == i) return fail(KHIP_E_UNSUPPORTED, "HAVING on a CORRELATION aggregate");
   }
   if (has_topk) {
     // merged list by list (TopkKudaf.merge) in the reference: not on the device
@@ -1806,6 +1873,8 @@ static khip_status compact_rows(khip_agg* a, const khip_having* h, std::vector<u
       return fail(KHIP_E_UNSUPPORTED, "HAVING on a TOPK / TOPKDISTINCT aggregate (an ARRAY)");
     if (agg_is_var(a->aggs[h->agg_index].kind))  // (nor the STDDEV kinds: decoded on the host from several words)
       return fail(KHIP_E_UNSUPPORTED, "HAVING on a STDDEV_SAMP / STDDEV_SAMPLE aggregate");
+    if (agg_is_pair(a->aggs[h->agg_index].kind))  // (nor CORRELATION, for the same reason)
+      return fail(KHIP_E_UNSUPPORTED, "HAVING on a CORRELATION aggregate");
     hd.active = 1;
     hd.op = h->op;
     hd.a = a->outs[h->agg_index];
@@ -2045,6 +2114,12 @@ static khip_status emit_snapshot(khip_agg* a, const std::vector<uint64_t>& rows,
           const bool big = o.type == KHIP_TYPE_INT64;
           dv = variance_result(o.kind == KHIP_AGG_STDDEV_SAMPLE, big, (int64_t)s[o.w_cnt], s[o.w_val],
                                big ? s[v.w_hi] : 0, &s[v.w_sq], big ? 4 : 2);
+          break;
+        }
+        case KHIP_AGG_CORRELATION: {  // never NULL: NaN below two pairs or for a constant argument (map :127-133)
+          const khip_agg::PairWords& v = a->out_pair[i];
+          dv = correlation_result(o.type == KHIP_TYPE_INT64, s[v.w_n], &s[v.w_sx], &s[v.w_sy], &s[v.w_sxx], &s[v.w_syy],
+                                  &s[v.w_sxy]);
           break;
         }
         case KHIP_AGG_AVG: {

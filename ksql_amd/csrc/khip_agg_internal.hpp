@@ -29,20 +29,31 @@ enum { P_ACCEPTED, P_NULL_KEY, P_NULL_ROW, P_BAD_TS, P_APPLIED, P_LATE, P_FAILED
 // u64 adds like OP_ADD_I64, of x >> 32 (arithmetic) and of the 32-bit limb op_slots(op) of x² (x
 // sign-extended, the square 128 bits wide): var_addend.  k_part_agg, k_apply and the table engine's
 // k_tagg_apply know them; a handle with one takes no other aggregate kernel (khip_agg::has_var).
+//
+// OP_PAIR_N / OP_PAIR_SUM / OP_PAIR_SQ / OP_PAIR_XY (CORRELATION over an INT or a BIGINT pair,
+// khip_correlation.hpp): plain u64 adds that apply only when op.col AND a second column, op_col2(op),
+// are both non-null — 1, a part of the value of op.col, a limb of its square, a limb of the signed
+// product of the two: pair_addend.  The same three kernels know them (khip_agg::has_pair).
 enum OpKind : int8_t {
-  OP_INC = 0, OP_INC_VALID, OP_ADD_I64, OP_ADD_F64, OP_MIN, OP_MAX, OP_TOPK, OP_TOPK_DISTINCT, OP_ADD_HI32, OP_ADD_SQ
+  OP_INC = 0, OP_INC_VALID, OP_ADD_I64, OP_ADD_F64, OP_MIN, OP_MAX, OP_TOPK, OP_TOPK_DISTINCT, OP_ADD_HI32, OP_ADD_SQ,
+  OP_PAIR_N, OP_PAIR_SUM, OP_PAIR_SQ, OP_PAIR_XY
 };
 
 struct UpdOp {
   int8_t kind;
   int8_t col;
   int16_t word;  // the state word; the TOPK kinds: first slot word | slots << 8 (state words are < 32);
-                 // OP_ADD_SQ: the word | limb index << 8
+                 // OP_ADD_SQ: the word | limb index << 8; the OP_PAIR kinds: the word | limb index << 8
+                 // | second column << 11 (MAX_COLS = 8) | (the pair is BIGINT) << 14
 };
 // (the slot count shares `word` so that the struct, and with it the parameter blocks and the code of
 // every kernel that never sees a TOPK op, stay what they were)
 __host__ __device__ __forceinline__ int op_word(const UpdOp& o) { return o.word & 0xFF; }
 __host__ __device__ __forceinline__ int op_slots(const UpdOp& o) { return (o.word >> 8) & 0xFF; }
+__host__ __device__ __forceinline__ bool op_is_pair(const UpdOp& o) { return o.kind >= OP_PAIR_N && o.kind <= OP_PAIR_XY; }
+__host__ __device__ __forceinline__ int op_limb(const UpdOp& o) { return (o.word >> 8) & 7; }
+__host__ __device__ __forceinline__ int op_col2(const UpdOp& o) { return (o.word >> 11) & 7; }
+__host__ __device__ __forceinline__ bool op_big(const UpdOp& o) { return (o.word >> 14) & 1; }
 
 // What OP_ADD_HI32 / OP_ADD_SQ add to their word for the argument x (INT: sign-extended).
 __device__ __forceinline__ uint64_t var_addend(const UpdOp& o, int64_t x) {
@@ -51,6 +62,36 @@ __device__ __forceinline__ uint64_t var_addend(const UpdOp& o, int64_t x) {
   const int j = op_slots(o);
   const uint64_t half = j < 2 ? m * m : __umul64hi(m, m);
   return (j & 1) ? half >> 32 : half & 0xFFFFFFFFull;
+}
+
+// What the OP_PAIR kinds add to their word for a record whose two arguments are both non-null:
+// x = the value of op.col, y = that of op_col2(op) (INT: sign-extended); op_big(op): a BIGINT pair.
+//   OP_PAIR_N    1
+//   OP_PAIR_SUM  INT: x;  BIGINT: limb 0 = x & 0xFFFFFFFF, limb 1 = x >> 32 (arithmetic)
+//   OP_PAIR_SQ   the 32-bit limb of x² (as OP_ADD_SQ: 2 limbs INT, 4 BIGINT)
+//   OP_PAIR_XY   INT: p = x y as int64, limb 0 = p & 0xFFFFFFFF, limb 1 = p >> 32 (arithmetic);
+//                BIGINT: p the 128-bit two's-complement product, limbs 0..2 unsigned, limb 3 = p >> 96
+//                (arithmetic)
+// Every addend is an unsigned 32-bit limb or a signed quantity of magnitude <= 2^31.
+__device__ __forceinline__ uint64_t pair_addend(const UpdOp& o, int64_t x, int64_t y) {
+  const int j = op_limb(o);
+  const bool big = op_big(o);
+  switch (o.kind) {
+    case OP_PAIR_N: return 1;
+    case OP_PAIR_SUM: return !big ? (uint64_t)x : (j == 0 ? (uint64_t)x & 0xFFFFFFFFull : (uint64_t)(x >> 32));
+    case OP_PAIR_SQ: {
+      const uint64_t m = x < 0 ? 0 - (uint64_t)x : (uint64_t)x;  // (Long.MIN_VALUE: 2^63)
+      const uint64_t half = j < 2 ? m * m : __umul64hi(m, m);
+      return (j & 1) ? half >> 32 : half & 0xFFFFFFFFull;
+    }
+    default: {  // OP_PAIR_XY
+      const uint64_t lo = (uint64_t)x * (uint64_t)y;  // (INT: the whole product, |p| <= 2^62)
+      if (!big) return j == 0 ? lo & 0xFFFFFFFFull : (uint64_t)((int64_t)lo >> 32);
+      if (j < 2) return j == 0 ? lo & 0xFFFFFFFFull : lo >> 32;
+      const int64_t hi = __mul64hi(x, y);  // the signed high half
+      return j == 2 ? (uint64_t)hi & 0xFFFFFFFFull : (uint64_t)(hi >> 32);
+    }
+  }
 }
 
 struct ApplyParams {
@@ -757,6 +798,15 @@ struct khip_agg {
   struct VarWords { int w_hi = -1, w_sq = -1; };
   std::vector<VarWords> out_var;
   bool has_var = false;
+  // ---- CORRELATION(x, y): out_pair[i] = the aggregate's words (khip_correlation.hpp) — the pair
+  // count and the first words of Σx, Σy (1 INT / 2 BIGINT), Σx², Σy² and Σxy (2 / 4 consecutive limb
+  // words each); w_n < 0: not a CORRELATION.  Runs are keyed by (quantity, column, gate column), the
+  // count and Σxy by the unordered pair: CORRELATION(y, x) shares every word of CORRELATION(x, y),
+  // CORRELATION(x, x) has one Σx and one Σx² run.  has_pair: the handle has OP_PAIR ops (gated like
+  // has_var).
+  struct PairWords { int w_n = -1, w_sx = -1, w_sy = -1, w_sxx = -1, w_syy = -1, w_sxy = -1; };
+  std::vector<PairWords> out_pair;
+  bool has_pair = false;
   int sw = 4;
   // table
   DevBuf table;

@@ -1447,8 +1447,16 @@ __device__ __forceinline__ void lds_apply(const PartAggParams& q, lds_i64* lw, i
       }
       default:  // OP_ADD_HI32 / OP_ADD_SQ (STDDEV: x >> 32 / a limb of x², khip_variance.hpp; ds_add_u64);
                 // here, so that the dispatch of the kinds above stays what it was
-        if (op.kind == OP_ADD_HI32 || op.kind == OP_ADD_SQ)
+        if (op.kind == OP_ADD_HI32 || op.kind == OP_ADD_SQ) {
           __hip_atomic_fetch_add((KLDS uint64_t*)w, var_addend(op, raw), WG_RLX);
+        } else if (op_is_pair(op)) {
+          // CORRELATION (khip_correlation.hpp): only a record with both arguments non-null counts
+          const int c2 = op_col2(op);
+          if (!((vmask >> c2) & 1u)) break;
+          const int cw2 = q.col_word[c2];
+          const int64_t raw2 = cw2 == 3 ? w3 : (int64_t)srec[(uint64_t)gi * q.rw + cw2];
+          __hip_atomic_fetch_add((KLDS uint64_t*)w, pair_addend(op, raw, raw2), WG_RLX);
+        }
         break;
     }
   }
@@ -3592,6 +3600,10 @@ khip_status part_init(khip_agg* a, int64_t hint) {
     if (a->ap.ops[o].kind == OP_INC) continue;
     s.vcols |= 1u << a->ap.ops[o].col;
     if (a->ap.ops[o].kind != OP_INC_VALID) colref[a->ap.ops[o].col] = true;
+    if (op_is_pair(a->ap.ops[o])) {  // (CORRELATION: the gate column's validity and value too)
+      s.vcols |= 1u << op_col2(a->ap.ops[o]);
+      colref[op_col2(a->ap.ops[o])] = true;
+    }
   }
   const bool meta = a->desc.window_kind == KHIP_WINDOW_HOPPING || s.vcols != 0;
   s.meta_word = meta ? 2 : -1;
@@ -3958,8 +3970,8 @@ static PartGeo part_plan(const khip_agg* a, int64_t n) {
   g.close0 = (a->windowed && a->host_stream_time >= 0) ? a->host_stream_time - a->grace : INT64_MIN;
   // which aggregate kernel pass 0 runs, as far as the host knows (k_part_wrange has the last word)
   // (a TOPK / TOPKDISTINCT handle: k_part_agg only — the merges have no plane form of the chain;
-  // a STDDEV handle too: the merges do not know its ops)
-  g.merge_allow = s.mH >= 256 && knob("KHIP_MERGE", 1) != 0 && !a->has_topk && !a->has_var;
+  // a STDDEV or CORRELATION handle too: the merges do not know its ops)
+  g.merge_allow = s.mH >= 256 && knob("KHIP_MERGE", 1) != 0 && !a->has_topk && !a->has_var && !a->has_pair;
   const int64_t r12_mode = knob("KHIP_R12", 1);  // 1: 12-byte records end to end; 2: pass A only
   g.r12_ok = g.narrow && !g.pad && g.merge_allow && r12_mode != 0;
   g.r12_merge = g.r12_ok && (r12_mode == 1 || !g.lvl2);  // what k_part_merge reads

@@ -274,8 +274,11 @@ __device__ __forceinline__ int64_t group_find(uint64_t* __restrict__ table, uint
 }
 
 // One op's net change from `add`'s contribution minus `sub`'s (the raw word: int64 for the
-// counts and integer sums, a double's bits for DOUBLE sums; 0 = unchanged).
-template <int NC>
+// counts and integer sums, a double's bits for DOUBLE sums; 0 = unchanged).  PAIR: the handle has
+// CORRELATION's OP_PAIR ops (khip_agg::has_pair); without it their code is not compiled in, so the
+// kernels of every other query stay what they were (the second column's picks and the 128-bit
+// product cost 1 to 4 VGPRs, and four instantiations a wave of occupancy, when always present).
+template <int NC, bool PAIR>
 __device__ __forceinline__ uint64_t op_delta(const UpdOp op, bool has_add, const TRow<NC>& add, bool has_sub,
                                              const TRow<NC>& sub) {
   const bool va = has_add && (op.kind == OP_INC || ((add.flags >> (8 + op.col)) & 1u));
@@ -296,6 +299,17 @@ __device__ __forceinline__ uint64_t op_delta(const UpdOp op, bool has_add, const
               // (khip_variance.hpp): undo = the word-wise difference, mod 2^64
       if (op.kind == OP_ADD_HI32 || op.kind == OP_ADD_SQ)
         return (va ? var_addend(op, wpick(add, op.col)) : 0) - (vs ? var_addend(op, wpick(sub, op.col)) : 0);
+      if constexpr (PAIR) {
+        // CORRELATION (khip_correlation.hpp): a row counts while both its arguments are non-null, so a
+        // change that turns the second column from NULL to a value is a pure add, the reverse a
+        // pure subtract
+        if (op_is_pair(op)) {
+          const int c2 = op_col2(op);
+          const bool pa = va && ((add.flags >> (8 + c2)) & 1u), ps = vs && ((sub.flags >> (8 + c2)) & 1u);
+          return (pa ? pair_addend(op, wpick(add, op.col), wpick(add, c2)) : 0) -
+                 (ps ? pair_addend(op, wpick(sub, op.col), wpick(sub, c2)) : 0);
+        }
+      }
       return 0;
   }
 }
@@ -361,7 +375,7 @@ __host__ __device__ constexpr int tagg_slot_words(int nc, bool u8, bool dense) {
 
 // Workgroup w takes sorted positions [w * TA_C, (w + 1) * TA_C); one thread per distinct PRIMARY
 // KEY (segment leader).  Hash layout: claimed[j] = the source slot the leader at j claimed, else -1.
-template <int NC, bool U8, bool DENSE>
+template <int NC, bool U8, bool DENSE, bool PAIR = false>
 __global__ __launch_bounds__(256) void k_tagg_apply(TaggArgs A, const uint64_t* __restrict__ skey,
                                                     const uint32_t* __restrict__ sidx, const uint64_t* __restrict__ rec,
                                                     const int64_t* __restrict__ gkeys, int64_t* __restrict__ claimed,
@@ -452,7 +466,7 @@ __global__ __launch_bounds__(256) void k_tagg_apply(TaggArgs A, const uint64_t* 
         __hip_atomic_fetch_max((int64_t*)&gsl[2], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       for (int q = 0; q < A.p.n_ops; q++) {
         const UpdOp op = A.p.ops[q];
-        op_add_atomic(op, &gsl[op_word(op)], op_delta<NC>(op, has_add, add, has_sub, sub));
+        op_add_atomic(op, &gsl[op_word(op)], op_delta<NC, PAIR>(op, has_add, add, has_sub, sub));
       }
     };
     // Replay the key's changes in arrival order.  Every change undoes the previous row from its
@@ -805,14 +819,18 @@ khip_status tagg_push(khip_agg* a, int64_t n, const int64_t* gkeys, const int64_
   A.dbase = T.dbase;
   using ApplyFn = void (*)(TaggArgs, const uint64_t*, const uint32_t*, const uint64_t*, const int64_t*, int64_t*,
                            unsigned long long*);
-#define KHIP_TAPPLY(U, D)                                                                                        \
-  {k_tagg_apply<0, U, D>, k_tagg_apply<1, U, D>, k_tagg_apply<2, U, D>, k_tagg_apply<3, U, D>,                  \
-   k_tagg_apply<4, U, D>, k_tagg_apply<5, U, D>, k_tagg_apply<6, U, D>, k_tagg_apply<7, U, D>,                  \
-   k_tagg_apply<8, U, D>}
-  static const ApplyFn kapply[2][2][MAX_COLS + 1] = {{KHIP_TAPPLY(false, false), KHIP_TAPPLY(true, false)},
-                                                     {KHIP_TAPPLY(false, true), KHIP_TAPPLY(true, true)}};
+#define KHIP_TAPPLY(U, D, P)                                                                                     \
+  {k_tagg_apply<0, U, D, P>, k_tagg_apply<1, U, D, P>, k_tagg_apply<2, U, D, P>, k_tagg_apply<3, U, D, P>,      \
+   k_tagg_apply<4, U, D, P>, k_tagg_apply<5, U, D, P>, k_tagg_apply<6, U, D, P>, k_tagg_apply<7, U, D, P>,      \
+   k_tagg_apply<8, U, D, P>}
+  // [a CORRELATION handle][dense][UTF8 group key][value columns]
+  static const ApplyFn kapply[2][2][2][MAX_COLS + 1] = {
+      {{KHIP_TAPPLY(false, false, false), KHIP_TAPPLY(true, false, false)},
+       {KHIP_TAPPLY(false, true, false), KHIP_TAPPLY(true, true, false)}},
+      {{KHIP_TAPPLY(false, false, true), KHIP_TAPPLY(true, false, true)},
+       {KHIP_TAPPLY(false, true, true), KHIP_TAPPLY(true, true, true)}}};
 #undef KHIP_TAPPLY
-  hipLaunchKernelGGL(kapply[T.dense][u8][nc], dim3(ceil_div(n, TA_C)), dim3(256), 0, st, A, kout, vout,
+  hipLaunchKernelGGL(kapply[a->has_pair][T.dense][u8][nc], dim3(ceil_div(n, TA_C)), dim3(256), 0, st, A, kout, vout,
                      T.rec.as<uint64_t>(), gkeys, T.claimed.as<int64_t>(), ctr);
   KHIP_TRY_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_tagg_grp_finalize, dim3(tgrid(n, 1024)), dim3(256), 0, st, a->table.as<uint64_t>(), a->sw,

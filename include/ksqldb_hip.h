@@ -887,6 +887,7 @@ khip_status khip_serde_destroy(khip_serde* s);
  *          158-161) → compact object in column order; DELIMITED: KsqlDelimitedSerializer
  *          (delimited/KsqlDelimitedSerializer.java:59-71; commons-csv 1.4 MINIMAL quoting, null =
  *          empty field); KAFKA: the single column's primitive bytes (a NULL column = a null value).
+ *          AVRO: see "AVRO values" below.
  *          A tombstone row (the row left the table / a HAVING delete) has a null value.
  * Numbers print as Long.toString / Double.toString (JDK 19+ shortest-decimal specification;
  * non-finite doubles as the JSON strings "NaN" / "Infinity" / "-Infinity", Jackson's default).
@@ -901,11 +902,12 @@ khip_status khip_serde_destroy(khip_serde* s);
  * BY_OFFSET), OR-ed into a khip_sink_desc.value_types entry like KHIP_AGG_K into a kind: no such
  * bits is a scalar column; KHIP_SINK_ARRAY(L), 1 <= L <= 32767, an ARRAY of the base type (INT32 /
  * INT64 / DOUBLE) with L slots per row, L being khip_agg_result_len() of the aggregate behind the
- * column (the sink has no 29-word limit of its own).  Only a JSON value carries one (the reference
- * rejects such a statement for DELIMITED and KAFKA at plan time): the column prints, after its
- * name, as the compact list [e0,e1,...], every element as a scalar of its type prints (a NULL
- * element as null, a non-finite DOUBLE as its string), the empty list as []; the column itself is
- * never SQL NULL.  The row's list: see khip_sink_rows.  KHIP_E_INVALID from khip_sink_create: an
+ * column (the sink has no 29-word limit of its own).  Only a JSON or an AVRO value carries one (the
+ * reference rejects such a statement for DELIMITED and KAFKA at plan time).  In JSON the column
+ * prints, after its name, as the compact list [e0,e1,...], every element as a scalar of its type
+ * prints (a NULL element as null, a non-finite DOUBLE as its string), the empty list as []; in
+ * AVRO it is one block (see "AVRO values").  The column itself is never SQL NULL.  The row's
+ * list: see khip_sink_rows.  KHIP_E_INVALID from khip_sink_create: an
  * ARRAY column with value format KAFKA or DELIMITED; the bits on a KHIP_SINK_SRC_WS / _WE column;
  * negative bits; two value columns reading one rows column with different L or base type when
  * either is an ARRAY.  Key columns are scalar: the bits on a key type are an unknown key type. */
@@ -917,10 +919,11 @@ typedef struct khip_sink_desc {
   const int32_t* key_types;        /* KHIP_TYPE_INT32 / INT64 / DOUBLE / STRING                   */
   const char* const* key_names;    /* JSON object field names (several key columns)              */
   int32_t window_kind;             /* KHIP_WINDOW_*: the table's window (NONE: plain key)        */
-  int32_t value_format;            /* KHIP_FMT_KAFKA / JSON / DELIMITED                          */
+  int32_t value_format;            /* KHIP_FMT_KAFKA / JSON / DELIMITED / AVRO                   */
   int32_t n_value_cols;            /* 0..KHIP_SINK_MAX_COLS (KAFKA: 1)                            */
   const int32_t* value_types;      /* KHIP_TYPE_INT32 / INT64 / DOUBLE [| KHIP_SINK_ARRAY(L)]     */
-  const char* const* value_names;  /* JSON field names, in output column order                   */
+  const char* const* value_names;  /* JSON field names, in output column order (AVRO: ignored,
+                                      may be NULL)                                               */
   const int32_t* value_src;        /* rows column index, or KHIP_SINK_SRC_WS / KHIP_SINK_SRC_WE   */
   int32_t delimiter;               /* DELIMITED: the delimiter byte (0 = ',')                     */
   int32_t device;
@@ -929,6 +932,35 @@ typedef struct khip_sink_desc {
 typedef struct khip_sink khip_sink;
 
 khip_status khip_sink_create(const khip_sink_desc* desc, khip_sink** out);
+
+/* AVRO values (value_format = KHIP_FMT_AVRO; keys stay KAFKA / JSON / DELIMITED, an AVRO key is
+ * KHIP_E_UNSUPPORTED).  The bytes of the reference's serializer for the schema ksqlDB itself
+ * generates: KsqlAvroSerdeFactory.createConnectSerializer (ksqldb-serde/src/main/java/io/confluent/
+ * ksql/serde/avro/KsqlAvroSerdeFactory.java:104-128) translates the row with AvroDataTranslator
+ * over AvroSchemas.getAvroCompatibleConnectSchema — every field optional, an array keeping its
+ * optional element schema (avro/AvroSchemas.java:135-142) — and Confluent's AvroConverter /
+ * KafkaAvroSerializer writes the record:
+ *   header  byte 0x00, the schema id as 4 bytes big-endian;
+ *   field   per value column in output order the union ["null", T]: the branch as an Avro int —
+ *           0x00 = NULL, 0x02 = present, then the value;
+ *   INT32 / INT64  zig-zag varint, (v << 1) ^ (v >> 31) / (v << 1) ^ (v >> 63): 7 bits a byte, least
+ *           significant group first, 0x80 on every byte but the last; at most 5 / 10 bytes;
+ *   DOUBLE  the 8 bytes of the IEEE bits little-endian as they are (doubleToRawLongBits: NaN
+ *           payloads, -0.0 and denormals survive);
+ *   KHIP_SINK_SRC_WS / _WE columns are BIGINT fields like any other;
+ *   ARRAY   the column is never SQL NULL: 0x02, then one block — a list of n >= 1 elements is the
+ *           long n, the n items (each a union branch and its value, a NULL element 0x00) and the
+ *           end byte 0x00; the empty list is the end byte alone.
+ * A sink with no value columns writes the 5 header bytes.  A tombstone row has a null value; unlike
+ * KAFKA, a row whose columns are all NULL has a value.  The binary form carries no names:
+ * value_names is ignored.
+ * The schema id is the one under which the Java side registered the sink topic's value schema
+ * (INTEGRATION.md); khip_sink_set_avro_schema_id may be called again between encodes, the next
+ * encode uses the new id.  KHIP_E_INVALID: a null handle, a negative id, a handle whose value
+ * format is not AVRO.  khip_sink_encode on an AVRO sink with no id set: KHIP_E_STATE.
+ * Not on this path (they stay with the reference): AVRO keys, a VALUE_SCHEMA_ID physical schema
+ * (plain or [T,"null"] fields), WRAP_SINGLE_VALUE=false, STRING / DECIMAL columns, PROTOBUF. */
+khip_status khip_sink_set_avro_schema_id(khip_sink* s, int32_t schema_id);
 
 /* One GROUP BY column of a batch (same memory kind as the batch). */
 typedef struct khip_key_col {

@@ -257,6 +257,7 @@ PRODUCT_ONLY = {
     "sink_create": ([C.POINTER(SinkDesc), C.POINTER(_P)]),
     "sink_key": ([_P, C.POINTER(Batch), C.POINTER(KeyCol), C.POINTER(Batch)]),
     "sink_encode": ([_P, C.POINTER(SinkRows), C.POINTER(SinkOut)]),
+    "sink_set_avro_schema_id": ([_P, i32]),
     "sink_sync": ([_P]),
     "sink_destroy": ([_P]),
 }
@@ -1115,10 +1116,11 @@ class SinkHandle:
     columns → the serialized composite key."""
 
     def __init__(self, lib, key_format, key_cols, value_format, value_cols, window_kind="NONE", delimiter=",",
-                 device=0):
+                 device=0, avro_schema_id=None):
         """key_cols: [(name, type)]; value_cols: [(name, type, src)] with src a rows column index or
         "WS" / "WE"; types INT32 / INT64 / DOUBLE / STRING (keys).  (name, type, src, L) is an ARRAY
-        column of L slots per row (KHIP_SINK_ARRAY(L); JSON values), type its element type."""
+        column of L slots per row (KHIP_SINK_ARRAY(L); JSON or AVRO values), type its element type.
+        avro_schema_id: the AVRO value format's schema id (set_avro_schema_id)."""
         self.lib = lib
         tmap = dict(TYPE, STRING=TYPE_STRING)
         nk, nv = len(key_cols), len(value_cols)
@@ -1137,6 +1139,12 @@ class SinkHandle:
                              self._vt, self._vn, self._vs, ord(delimiter), device)
         self.h = C.c_void_p()
         lib.check(lib.sink_create(C.byref(self.desc), C.byref(self.h)), "sink_create")
+        if avro_schema_id is not None:
+            self.set_avro_schema_id(avro_schema_id)
+
+    def set_avro_schema_id(self, schema_id):
+        """khip_sink_set_avro_schema_id: the id in the header of the AVRO values encoded from now on."""
+        self.lib.check(self.lib.sink_set_avro_schema_id(self.h, int(schema_id)), "sink_set_avro_schema_id")
 
     def key(self, batch, cols):
         """batch: a HostBatch (host columns) or any batch object with .struct; cols: per key column

@@ -13,7 +13,9 @@
 // window suffix leave as 8-byte words), and a JSON column's '{' / ',' + escaped name + ':' is built
 // once on the host.  A sink with an ARRAY value column (KHIP_SINK_ARRAY: JSON lists) runs its own
 // instantiations, k_sink_measure<true> and k_sink_write_arr; a scalar sink's kernels carry none
-// of it.  Doubles print
+// of it.  A sink with AVRO values (the Confluent wire format of ksqlDB's own schema: scalars and
+// ARRAY columns, keys as above) runs three kernels of its own, "the AVRO sink's kernels" below: the
+// lengths in closed form, the same two stages on the way out.  Doubles print
 // through the Schubfach shortest-decimal algorithm (R. Giulietti 2020; java.lang.Double.toString
 // since JDK 19) with the 126-bit powers of ten of tools/gen_dtoa.py, so every digit is computed
 // exactly with 64-bit integer arithmetic.  Byte parity of DOUBLE text therefore assumes the
@@ -60,7 +62,7 @@ struct SinkParams {
   int32_t kpre_len[SK_MAX], vpre_len[SK_MAX];
   alignas(8) uint8_t kpre[SK_MAX][SK_PRE];
   alignas(8) uint8_t vpre[SK_MAX][SK_PRE];
-  // ARRAY value columns (JSON values only): the slots per row, KHIP_SINK_ARRAY's L; 0 = the scalar
+  // ARRAY value columns (JSON and AVRO values): the slots per row, KHIP_SINK_ARRAY's L; 0 = the scalar
   // column (vtype is the element type either way)
   int32_t varr[SK_MAX];
 };
@@ -491,6 +493,68 @@ __device__ __forceinline__ void put_value(W& w, const SinkParams& q, F&& vval, G
   }
 }
 
+// ------------------------------------------------------------------ AVRO values
+//
+// The Confluent wire format of the record ksqlDB's own schema describes (include/ksqldb_hip.h,
+// "AVRO values"): byte 0, the schema id big-endian, then per column the union ["null", T] — branch
+// 0 for NULL, branch 1 (the byte 0x02) and the value.  The AVRO sink runs kernels of its own
+// (k_sink_measure_avro, k_sink_write_avro, k_sink_write_arr_avro): put_value and the kernels of the
+// other formats carry none of this.
+
+__device__ __forceinline__ uint64_t avro_zz(int64_t v) { return ((uint64_t)v << 1) ^ (uint64_t)(v >> 63); }
+// bytes of the varint of u: seven bits a byte
+__device__ __forceinline__ int avro_varint_len(uint64_t u) { return (63 - __clzll((long long)(u | 1))) / 7 + 1; }
+
+template <class W>
+__device__ __forceinline__ void put_avro_varint(W& w, uint64_t u) {
+  while (u >> 7) {
+    w.put((uint8_t)(u | 0x80));
+    u >>= 7;
+  }
+  w.put((uint8_t)u);
+}
+
+// An optional INT32 / INT64 (v.i sign-extended: an int's zig-zag is the long's) or DOUBLE (the raw
+// bits, little-endian).
+template <class W>
+__device__ __forceinline__ void put_avro_val(W& w, int type, const Val& v) {
+  if (v.null) {
+    w.put(0);
+    return;
+  }
+  w.put(2);
+  if (type == KHIP_TYPE_DOUBLE) {
+#pragma unroll
+    for (int b = 0; b < 8; b++) w.put((uint8_t)((uint64_t)v.i >> (8 * b)));
+  } else {
+    put_avro_varint(w, avro_zz(v.i));
+  }
+}
+__device__ __forceinline__ int avro_val_len(int type, const Val& v) {
+  return v.null ? 1 : type == KHIP_TYPE_DOUBLE ? 9 : 1 + avro_varint_len(avro_zz(v.i));
+}
+
+// vcount(c): the length of the row's list in ARRAY column c; velem as for put_value.  A list is one
+// block (its length, its items, the end byte 0); the empty list is the end byte alone.
+template <bool ARR, class W, class F, class C, class G>
+__device__ __forceinline__ void put_avro_value(W& w, const SinkParams& q, int32_t schema_id, F&& vval, C&& vcount,
+                                               G&& velem) {
+  w.put(0);
+  put_be(w, (uint64_t)(uint32_t)schema_id, 4);
+  for (int i = 0; i < q.n_val; i++) {
+    if (ARR && q.varr[i] > 0) {
+      w.put(2);
+      const int cnt = vcount(i);
+      if (cnt) put_avro_varint(w, (uint64_t)cnt << 1);
+      Val v;
+      for (int e = 0; e < cnt && velem(i, e, v); e++) put_avro_val(w, q.vtype[i], v);
+      w.put(0);
+      continue;
+    }
+    put_avro_val(w, q.vtype[i], vval(i));
+  }
+}
+
 // ------------------------------------------------------------------ rows → records
 
 struct RowsDev {
@@ -875,6 +939,187 @@ __global__ KHIP_SINK_WRITE_LB void k_sink_write_arr(const SinkParams* __restrict
   }
 }
 
+// ------------------------------------------------------------------ the AVRO sink's kernels
+//
+// The value format AVRO has its own three kernels, with the structure of the three above (tiles,
+// offsets, keys, outputs and stages are theirs), so that the other formats' kernels stay as they
+// are.  What differs: the measure pass computes a value's length in closed form (no byte writer
+// runs), the encoder is put_avro_value, and a staged row goes to LDS through an LDS pointer (DS
+// stores, not FLAT ones).
+
+// the length of row i's list in ARRAY column c: row_elem's rule, the null bytes alone
+__device__ __forceinline__ int row_list_len(const SinkParams& q, const RowsDev& r, int64_t i, int c) {
+  const int L = q.varr[c];
+  const uint8_t* nb = r.cnull[q.vsrc[c]] + i * L;
+  int e = 0;
+  while (e < L && (nb[e] == 0 || nb[e] == 2)) e++;
+  return e;
+}
+
+// the bytes put_avro_value writes for row i
+template <bool ARR>
+__device__ __forceinline__ int64_t avro_value_len(const SinkParams& q, const RowsDev& r, int64_t i) {
+  int64_t len = 5;
+  for (int c = 0; c < q.n_val; c++) {
+    if (ARR && q.varr[c] > 0) {
+      Val v;
+      int e = 0;
+      for (; row_elem(q, r, i, c, e, v); e++) len += avro_val_len(q.vtype[c], v);
+      len += e ? 2 + avro_varint_len((uint64_t)e << 1) : 2;
+      continue;
+    }
+    len += avro_val_len(q.vtype[c], row_value_val(q, r, i, c));
+  }
+  return len;
+}
+
+struct LdsW {  // MemW into LDS
+  sk_lds_u8* p;
+  __device__ __forceinline__ void put(uint8_t c) { *p++ = c; }
+};
+
+template <bool ARR>
+__global__ __launch_bounds__(256) void k_sink_measure_avro(const SinkParams* __restrict__ qp, RowsDev r, int64_t n,
+                                                           int kfix, int64_t nT, int64_t* __restrict__ klen,
+                                                           int64_t* __restrict__ vlen, int64_t* __restrict__ tsum) {
+  __shared__ int64_t ws[2][4];
+  const SinkParams& q = *qp;
+  static_assert(SK_TR == 1, "one row per thread");
+  const int64_t i = (int64_t)blockIdx.x * SK_TILE + threadIdx.x;
+  int64_t sk = 0, sv = 0;
+  if (i < n) {
+    if (!kfix) {
+      CountW kw;
+      encode_key_row(kw, q, r, i);
+      klen[i + 1] = sk = kw.n;
+    }
+    if (!value_is_null(q, r, i)) sv = avro_value_len<ARR>(q, r, i);
+    vlen[i + 1] = sv;
+  }
+  sk_block_sum2(sk, sv, ws);
+  if (threadIdx.x == 0) {
+    tsum[1 + blockIdx.x] = sk;
+    tsum[nT + 2 + blockIdx.x] = sv;
+  }
+}
+
+// k_sink_write for AVRO values: the per-wave stage and the byte-wise way of a wave past SK_WBUF.
+__global__ KHIP_SINK_WRITE_LB void k_sink_write_avro(const SinkParams* __restrict__ qp, RowsDev r, int64_t n, int kfix,
+                                                     int kwords, int64_t nT, const int64_t* __restrict__ tsum,
+                                                     int64_t* __restrict__ koff, uint8_t* __restrict__ kb,
+                                                     int64_t* __restrict__ voff, uint8_t* __restrict__ vb,
+                                                     uint8_t* __restrict__ vnull, int32_t schema_id) {
+  __shared__ int64_t ws[2][4];
+  __shared__ uint32_t vst[4][SK_WBUF / 4 + 4];
+  const SinkParams& q = *qp;
+  const int wave = threadIdx.x >> 6;
+  const int64_t i = (int64_t)blockIdx.x * SK_TILE + threadIdx.x;
+  const bool in = i < n;
+  const int64_t kl = !in ? 0 : kfix ? kfix : koff[i + 1];
+  const int64_t vl = in ? voff[i + 1] : 0;
+  int64_t ko = kl, vo = vl, tk, tv;
+  sk_block_scan2(ko, vo, tk, tv, ws);
+  ko += kfix ? (int64_t)blockIdx.x * SK_TILE * kfix : tsum[blockIdx.x];
+  vo += tsum[nT + 1 + blockIdx.x];
+  const int64_t wbase = __shfl(vo, 0, 64), wlen = __shfl(vo + vl, 63, 64) - wbase;  // past-n lanes: vl 0
+  const bool staged = wlen <= SK_WBUF;
+  const bool isnull = in ? value_is_null(q, r, i) : true;
+  Val v0{0, nullptr, 0, true}, v1 = v0, v2 = v0, v3 = v0;  // the first four value columns
+  if (!isnull) {
+    if (q.n_val > 0) v0 = row_value_val(q, r, i, 0);
+    if (q.n_val > 1) v1 = row_value_val(q, r, i, 1);
+    if (q.n_val > 2) v2 = row_value_val(q, r, i, 2);
+    if (q.n_val > 3) v3 = row_value_val(q, r, i, 3);
+  }
+  auto vget = [&](int c) {
+    return c == 0 ? v0 : c == 1 ? v1 : c == 2 ? v2 : c == 3 ? v3 : row_value_val(q, r, i, c);
+  };
+  auto no_count = [](int) { return 0; };  // (a scalar sink has no ARRAY column)
+  auto no_elem = [](int, int, Val&) { return false; };
+  if (staged && !isnull) {
+    LdsW vw{(sk_lds_u8*)vst[wave] + (vo - wbase)};
+    put_avro_value<false>(vw, q, schema_id, vget, no_count, no_elem);
+  }
+  __syncthreads();
+  if (staged && wlen > 0) sk_wave_copy((const uint8_t*)vst[wave], (int)wlen, vb + wbase);
+  if (in) {
+    if (kwords) {
+      put_key_words(q, r, i, (uint64_t*)(kb + ko));
+    } else {
+      MemW kw{kb + ko};
+      encode_key_row(kw, q, r, i);
+    }
+    sk_st(vnull + i, (uint8_t)(isnull ? 1 : 0));
+    if (!staged && !isnull) {
+      MemW vw{vb + vo};
+      put_avro_value<false>(vw, q, schema_id, vget, no_count, no_elem);
+    }
+    sk_st(koff + i + 1, ko + kl);
+    sk_st(voff + i + 1, vo + vl);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    koff[0] = 0;
+    voff[0] = 0;
+  }
+}
+
+// k_sink_write_arr for AVRO values: the tile's stage in rounds of SK_ABUF bytes through WinW.
+__global__ KHIP_SINK_WRITE_LB void k_sink_write_arr_avro(const SinkParams* __restrict__ qp, RowsDev r, int64_t n,
+                                                         int kfix, int kwords, int64_t nT,
+                                                         const int64_t* __restrict__ tsum, int64_t* __restrict__ koff,
+                                                         uint8_t* __restrict__ kb, int64_t* __restrict__ voff,
+                                                         uint8_t* __restrict__ vb, uint8_t* __restrict__ vnull,
+                                                         int32_t schema_id) {
+  __shared__ int64_t ws[2][4];
+  __shared__ uint32_t ast[SK_ABUF / 4 + 4];
+  const SinkParams& q = *qp;
+  const int64_t i = (int64_t)blockIdx.x * SK_TILE + threadIdx.x;
+  const bool in = i < n;
+  const int64_t kl = !in ? 0 : kfix ? kfix : koff[i + 1];
+  const int64_t vl = in ? voff[i + 1] : 0;
+  int64_t ko = kl, vo = vl, tk, tv;
+  sk_block_scan2(ko, vo, tk, tv, ws);
+  ko += kfix ? (int64_t)blockIdx.x * SK_TILE * kfix : tsum[blockIdx.x];
+  const int64_t tbase = tsum[nT + 1 + blockIdx.x];  // the tile's first value byte; vo: the row's, within the tile
+  const bool isnull = in ? value_is_null(q, r, i) : true;
+  Val v0{0, nullptr, 0, true}, v1 = v0, v2 = v0, v3 = v0;  // the first four value columns (scalars)
+  if (!isnull) {
+    if (q.n_val > 0 && !q.varr[0]) v0 = row_value_val(q, r, i, 0);
+    if (q.n_val > 1 && !q.varr[1]) v1 = row_value_val(q, r, i, 1);
+    if (q.n_val > 2 && !q.varr[2]) v2 = row_value_val(q, r, i, 2);
+    if (q.n_val > 3 && !q.varr[3]) v3 = row_value_val(q, r, i, 3);
+  }
+  auto vget = [&](int c) {
+    return c == 0 ? v0 : c == 1 ? v1 : c == 2 ? v2 : c == 3 ? v3 : row_value_val(q, r, i, c);
+  };
+  const uint8_t* als = (const uint8_t*)ast;
+  for (int64_t lo = 0; lo < tv; lo += SK_ABUF) {
+    if (!isnull && vo < lo + SK_ABUF && vo + vl > lo) {
+      WinW vw{(sk_lds_u8*)ast, vo - lo};
+      put_avro_value<true>(vw, q, schema_id, vget, [&](int c) { return row_list_len(q, r, i, c); },
+                           [&](int c, int e, Val& v) { return row_elem(q, r, i, c, e, v); });
+    }
+    __syncthreads();
+    sk_range_copy<256>(als, (int)(tv - lo < SK_ABUF ? tv - lo : SK_ABUF), vb + tbase + lo, threadIdx.x);
+    __syncthreads();
+  }
+  if (in) {
+    if (kwords) {
+      put_key_words(q, r, i, (uint64_t*)(kb + ko));
+    } else {
+      MemW kw{kb + ko};
+      encode_key_row(kw, q, r, i);
+    }
+    sk_st(vnull + i, (uint8_t)(isnull ? 1 : 0));
+    sk_st(koff + i + 1, ko + kl);
+    sk_st(voff + i + 1, tbase + vo + vl);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    koff[0] = 0;
+    voff[0] = 0;
+  }
+}
+
 // ------------------------------------------------------------------ GROUP BY columns → key bytes
 
 struct KeySrcDev {
@@ -1005,6 +1250,7 @@ struct khip_sink {
   SinkParams q{};
   int device = 0;
   bool has_arr = false;        // some value column is an ARRAY: the k_sink_*<true> / _arr kernels
+  int32_t avro_id = -1;        // AVRO values: the schema id of the records' header; -1 = not set yet
   int32_t src_len[SK_MAX] = {};  // per rows column: its ARRAY length L, 0 = scalar
   hipStream_t stream = nullptr;
   DevBuf dq, bsum, bsum2, tsum, koff, kbytes, kvalid, voff, vbytes, vnull;
@@ -1057,8 +1303,8 @@ khip_status khip_sink_create(const khip_sink_desc* d, khip_sink** out) {
   const int kf = d->key_format, vf = d->value_format;
   if (kf != KHIP_FMT_KAFKA && kf != KHIP_FMT_JSON && kf != KHIP_FMT_DELIMITED)
     return fail(KHIP_E_UNSUPPORTED, "sink key format (KAFKA, JSON, DELIMITED)");
-  if (vf != KHIP_FMT_KAFKA && vf != KHIP_FMT_JSON && vf != KHIP_FMT_DELIMITED)
-    return fail(KHIP_E_UNSUPPORTED, "sink value format (KAFKA, JSON, DELIMITED)");
+  if (vf != KHIP_FMT_KAFKA && vf != KHIP_FMT_JSON && vf != KHIP_FMT_DELIMITED && vf != KHIP_FMT_AVRO)
+    return fail(KHIP_E_UNSUPPORTED, "sink value format (KAFKA, JSON, DELIMITED, AVRO)");
   if (d->n_key_cols < 1 || d->n_key_cols > SK_MAX || !d->key_types) return fail(KHIP_E_INVALID, "1..32 key columns");
   if (kf == KHIP_FMT_KAFKA && d->n_key_cols != 1)
     return fail(KHIP_E_UNSUPPORTED, "the KAFKA key format carries one column");
@@ -1104,9 +1350,9 @@ khip_status khip_sink_create(const khip_sink_desc* d, khip_sink** out) {
     q.vtype[i] = d->value_types[i] & 0xFFFF;
     q.varr[i] = d->value_types[i] >> 16;  // KHIP_SINK_ARRAY(L): 1..32767, 0 = scalar
     q.vsrc[i] = d->value_src[i];
-    if (q.varr[i] && vf != KHIP_FMT_JSON) {
+    if (q.varr[i] && vf != KHIP_FMT_JSON && vf != KHIP_FMT_AVRO) {
       delete s;
-      return fail(KHIP_E_INVALID, "an ARRAY value column needs the JSON value format (KAFKA / DELIMITED carry no arrays)");
+      return fail(KHIP_E_INVALID, "an ARRAY value column needs the JSON or AVRO value format (KAFKA / DELIMITED carry no arrays)");
     }
     if (q.varr[i] && (q.vsrc[i] == KHIP_SINK_SRC_WS || q.vsrc[i] == KHIP_SINK_SRC_WE)) {
       delete s;
@@ -1162,6 +1408,15 @@ khip_status khip_sink_create(const khip_sink_desc* d, khip_sink** out) {
     return st;
   }
   *out = s;
+  return KHIP_OK;
+}
+
+khip_status khip_sink_set_avro_schema_id(khip_sink* s, int32_t schema_id) {
+  clear_error();
+  if (!s) return fail(KHIP_E_INVALID, "null argument");
+  if (s->q.value_format != KHIP_FMT_AVRO) return fail(KHIP_E_INVALID, "a schema id belongs to the AVRO value format");
+  if (schema_id < 0) return fail(KHIP_E_INVALID, "negative schema id");
+  s->avro_id = schema_id;
   return KHIP_OK;
 }
 
@@ -1242,6 +1497,8 @@ khip_status khip_sink_encode(khip_sink* s, const khip_sink_rows* rows, khip_sink
   clear_error();
   if (!s || !rows || !out) return fail(KHIP_E_INVALID, "null argument");
   const SinkParams& q = s->q;
+  const bool avro = q.value_format == KHIP_FMT_AVRO;
+  if (avro && s->avro_id < 0) return fail(KHIP_E_STATE, "AVRO values need khip_sink_set_avro_schema_id first");
   const int64_t n = rows->n_rows;
   if (n < 0 || !out->key_offsets || !out->value_offsets || !out->value_null) return fail(KHIP_E_INVALID, "rows / outputs");
   const bool windowed = q.window_kind != KHIP_WINDOW_NONE;
@@ -1333,8 +1590,12 @@ khip_status khip_sink_encode(khip_sink* s, const khip_sink_rows* rows, khip_sink
   if (n) {
     KHIP_TRY(s->tsum.ensure((size_t)(2 * (nT + 1)) * 8));
     int64_t* ts = s->tsum.as<int64_t>();
-    hipLaunchKernelGGL(s->has_arr ? k_sink_measure<true> : k_sink_measure<false>, dim3((unsigned)nT), dim3(256), 0, s->stream,
-                       s->dq.as<SinkParams>(), r, n, kfix, nT, koff, voff, ts);
+    if (avro)
+      hipLaunchKernelGGL(s->has_arr ? k_sink_measure_avro<true> : k_sink_measure_avro<false>, dim3((unsigned)nT), dim3(256), 0,
+                         s->stream, s->dq.as<SinkParams>(), r, n, kfix, nT, koff, voff, ts);
+    else
+      hipLaunchKernelGGL(s->has_arr ? k_sink_measure<true> : k_sink_measure<false>, dim3((unsigned)nT), dim3(256), 0, s->stream,
+                         s->dq.as<SinkParams>(), r, n, kfix, nT, koff, voff, ts);
     KHIP_TRY_HIP(hipGetLastError());
     int64_t tk = 0, tv = 0;
     if (!kfix) KHIP_TRY(sk_scan(s, s->bsum, ts, nT, &tk, false));
@@ -1365,8 +1626,13 @@ khip_status khip_sink_encode(khip_sink* s, const khip_sink_rows* rows, khip_sink
   }
   if (n) {
     const int kwords = kfix && q.ktype[0] == KHIP_TYPE_INT64 && ((uintptr_t)kb & 7) == 0 ? kfix / 8 : 0;
-    hipLaunchKernelGGL(s->has_arr ? k_sink_write_arr : k_sink_write, dim3((unsigned)nT), dim3(256), 0, s->stream,
-                       s->dq.as<SinkParams>(), r, n, kfix, kwords, nT, s->tsum.as<int64_t>(), koff, kb, voff, vb, vn);
+    if (avro)
+      hipLaunchKernelGGL(s->has_arr ? k_sink_write_arr_avro : k_sink_write_avro, dim3((unsigned)nT), dim3(256), 0, s->stream,
+                         s->dq.as<SinkParams>(), r, n, kfix, kwords, nT, s->tsum.as<int64_t>(), koff, kb, voff, vb, vn,
+                         s->avro_id);
+    else
+      hipLaunchKernelGGL(s->has_arr ? k_sink_write_arr : k_sink_write, dim3((unsigned)nT), dim3(256), 0, s->stream,
+                         s->dq.as<SinkParams>(), r, n, kfix, kwords, nT, s->tsum.as<int64_t>(), koff, kb, voff, vb, vn);
     KHIP_TRY_HIP(hipGetLastError());
   }
   if (!dev_out) {

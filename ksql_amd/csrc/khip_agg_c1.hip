@@ -8,17 +8,26 @@
 //
 //   k_c1_scatter  keys, ts, validity: every record → (key - kb, ts - T0), two int32s; invalid
 //                 records (null key / row, ts < 0) as sentinels; each 4096-record step leaves as
-//                 one run in bucket order (B coarse buckets: top bits of the key hash) with its
-//                 per-bucket counts (the step-run layout: no histogram pass ahead of it); per step
-//                 the largest and smallest accepted ts, per tile the counters and the key range.
+//                 one run in bucket order (B coarse buckets: top bits of the key hash; the
+//                 step-run layout: no histogram pass ahead of it).  A tile (16 steps) leaves, per
+//                 bucket, each run's place within the tile's share of the bucket (u16, the prefix
+//                 over the tile's steps, formed in LDS) and the tile's total; per step the largest
+//                 and smallest accepted ts, per tile the counters and the key range.
 //                 Optimistic: no record is assumed late.
-//   (scan_excl over the [bucket][step] counts: each run's place in its bucket; k_c1_bases)
+//   k_c1_runpos   one workgroup per bucket: the exclusive scan of the bucket's tile totals (each
+//                 tile's base in the bucket) and the bucket's total.  A run's place in its
+//                 bucket = tile base + place within the tile (run_pos): two levels, no scan over
+//                 the [bucket][step] counts.
 //   k_c1_check    one workgroup: stream time before each 4096-record step (exclusive prefix
 //                 max), and the push is ACCEPTED only if no step can hold a late record (the
 //                 general path's `fast` test per step), every ts fits ts - T0 in 31 bits and the
 //                 keys fit 32 bits above the base kb; otherwise nothing was written and the host
 //                 runs the general path (or the same push with kb = the key minimum).
-//                 Also the window range, the group-identity width and the refine's chunk list.
+//                 Also the bucket bases (from the bucket totals), the window range, the
+//                 group-identity width, the refine's chunk list and, when accepted, the push's
+//                 statistics (the tiles' counters summed: no k_part_stats launch).
+//   k_c1_chunks   one thread per refine chunk: its first step run and run count (two searches,
+//                 each over the tile bases and then the tile's steps)
 //   k_c1_refine   per 8K-record chunk of a bucket, read from its step runs: sentinels dropped,
 //                 keys rebased to the key minimum, records counting-sorted by their partition
 //                 inside the bucket (LDS), written bucket-contiguously; the chunk's per-partition
@@ -42,7 +51,6 @@
 #include <vector>
 
 #include "khip_part.hpp"
-#include "khip_sort.hpp"
 
 namespace khip {
 
@@ -75,10 +83,14 @@ __device__ __forceinline__ int64_t ci_ld(const int64_t* ci, int k) {
 // ------------------------------------------------------------------ step-run layout
 // The scatters write no bucket-contiguous output (that needs every tile's bucket counts first: a
 // histogram pass over the keys): each step of S records leaves as ONE contiguous run of S records
-// in bucket order at out[gs * S], and its per-bucket count / offset go to rcnt[b][gs] / roff[b][gs]
-// (bucket-major; held in LDS for the tile's steps and written per bucket at its end).  The exclusive scan of rcnt gives each (bucket, step) run's place in the bucket's
-// order (rpos); the refine reads a bucket's chunk from its step runs.  The key range, the time base
-// and the bucket counts are all learned in the one read of the input.
+// in bucket order at out[gs * S]; its per-bucket counts / offsets are held in LDS for the tile's
+// SPT steps and leave per bucket at the tile's end (flush_run_counts): roff[b][gs], the bucket's
+// offset inside step gs's run; rloc[b][gs], the run's place within the tile's share of the bucket
+// (the exclusive prefix of the counts over the tile's steps); ttot[b][tile], the tile's total.
+// k_c1_runpos scans each bucket's tile totals (tbase[b][0 .. nT], the last the bucket's total), and
+// run_pos gives a (bucket, step) run's place in the bucket's order; the refine reads a bucket's
+// chunk from its step runs.  The key range, the time base and the bucket counts are all learned in
+// the one read of the input.
 template <int U, int NT, class R, bool W>
 __device__ __forceinline__ uint32_t stage_step_runs(const R (&rec)[U], const uint32_t (&t32)[U], const uint32_t (&bin)[U],
                                                 const bool (&ok)[U], int nb, uint32_t* cnt, uint32_t* sbase, int* wsum,
@@ -162,36 +174,50 @@ __host__ __device__ constexpr size_t run_stage_lds(int nb, int S, int rec_bytes,
 // the end of the tile
 __host__ __device__ constexpr size_t run_cnt_lds(int nb, int spt) { return (size_t)nb * spt * 6; }
 
-// The tile's SPT run counts / offsets of bucket b leave as whole 16-byte stores (rcnt[b][t * SPT ..],
-// roff[b][t * SPT ..]: 64 + 32 B for SPT = 16) instead of a 4-byte and a 2-byte store per step and
-// bucket, which the memory side turned into 32-byte partial writes (C2: ~250 MB a push).  Steps
-// past the input (the last tile's) are empty runs.  Thread b wrote row entries lrc[st][b] itself.
+// The tile's SPT run places / offsets of bucket b leave as whole 16-byte stores (rloc[b][t * SPT ..],
+// roff[b][t * SPT ..]: 32 + 32 B for SPT = 16) instead of 2-byte stores per step and bucket, which
+// the memory side turned into 32-byte partial writes (C2: ~250 MB a push).  A run's place is the
+// sum of the bucket's counts over the tile's earlier steps: at most C1_TILE less one step, a u16.
+// Steps past the input (the last tile's) are empty runs at the end of the tile's share.  Thread b
+// wrote row entries lrc[st][b] itself.
 template <int SPT, int NT>
 __device__ __forceinline__ void flush_run_counts(const uint32_t* lrc, const uint16_t* lro, int B, int st_last, int64_t t,
-                                                 int64_t nSt, uint32_t* __restrict__ rcnt, uint16_t* __restrict__ roff) {
+                                                 int64_t nT, uint16_t* __restrict__ rloc, uint16_t* __restrict__ roff,
+                                                 uint32_t* __restrict__ ttot) {
   static_assert(SPT % 8 == 0, "whole 16-byte stores");
+  static_assert(C1_TILE - C1_TILE / SPT < 65536, "a run's place within its tile fits a u16");
+  const int64_t nSt = nT * SPT;
   for (int b = threadIdx.x; b < B; b += NT) {
-    uint32_t* rc = rcnt + (int64_t)b * nSt + t * SPT;
+    uint16_t* rl = rloc + (int64_t)b * nSt + t * SPT;
     uint16_t* ro = roff + (int64_t)b * nSt + t * SPT;
-#pragma unroll
-    for (int q = 0; q < SPT / 4; q++) {
-      uint32_t v[4];
-#pragma unroll
-      for (int k = 0; k < 4; k++) v[k] = 4 * q + k <= st_last ? lrc[(4 * q + k) * B + b] : 0u;
-      *(uint4*)(rc + 4 * q) = make_uint4(v[0], v[1], v[2], v[3]);
-    }
+    uint32_t acc = 0u;
 #pragma unroll
     for (int q = 0; q < SPT / 8; q++) {
-      uint32_t w[4];
+      uint32_t v[4], w[4];
 #pragma unroll
       for (int k = 0; k < 4; k++) {
         const int s0 = 8 * q + 2 * k;
+        const uint32_t p0 = acc;
+        acc += s0 <= st_last ? lrc[s0 * B + b] : 0u;
+        const uint32_t p1 = acc;
+        acc += s0 + 1 <= st_last ? lrc[(s0 + 1) * B + b] : 0u;
+        v[k] = p0 | p1 << 16;
         const uint32_t lo = s0 <= st_last ? lro[s0 * B + b] : 0u, hi = s0 + 1 <= st_last ? lro[(s0 + 1) * B + b] : 0u;
         w[k] = lo | hi << 16;
       }
+      *(uint4*)(rl + 8 * q) = make_uint4(v[0], v[1], v[2], v[3]);
       *(uint4*)(ro + 8 * q) = make_uint4(w[0], w[1], w[2], w[3]);
     }
+    ttot[(int64_t)b * nT + t] = acc;
   }
+}
+
+// A (bucket, step) run's place in its bucket's order: the tile's base (tb: the bucket's row of
+// k_c1_runpos's scan, nT + 1 entries) + the run's place within the tile (rl: the bucket's row of
+// rloc).  s = nSt: the bucket's total, the end of its last run.  sh = log2 of the steps per tile.
+__device__ __forceinline__ int64_t run_pos(const uint32_t* __restrict__ tb, const uint16_t* __restrict__ rl, int64_t nSt,
+                                           int sh, int64_t s) {
+  return (int64_t)tb[s >> sh] + (s < nSt ? (int64_t)rl[s] : 0);
 }
 
 // The time base, the key base and the tile's key range — shared by both scatters.  T0: the stream
@@ -230,8 +256,8 @@ __device__ __forceinline__ void run_krange(const uint32_t* lkr, int kfail, int64
 template <int U, int NT, bool WIDE, bool ST>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_c1_scatter(
     const int64_t* __restrict__ keys, const int64_t* __restrict__ ts, const uint8_t* __restrict__ kv,
-    const uint8_t* __restrict__ rv, int64_t n, int64_t nT, int log2B, uint32_t* __restrict__ rcnt,
-    uint16_t* __restrict__ roff, int64_t nSt, uint64_t* __restrict__ srec, int64_t* __restrict__ tilestat,
+    const uint8_t* __restrict__ rv, int64_t n, int64_t nT, int log2B, uint16_t* __restrict__ rloc,
+    uint16_t* __restrict__ roff, uint32_t* __restrict__ ttot, uint64_t* __restrict__ srec, int64_t* __restrict__ tilestat,
     int64_t* __restrict__ tpart, int64_t* __restrict__ ci, const int64_t* __restrict__ st_at,
     uint32_t* __restrict__ srecT, int64_t size, int64_t adv, FastDiv fd, int64_t grace,
     const int64_t* __restrict__ stream_time, int64_t kb_in, int has_kb) {
@@ -368,7 +394,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
     }
     if (threadIdx.x == 0 && st > 0) publish(s0 - S, st - 1);
   }
-  flush_run_counts<SPT, NT>(lrc, lro, B, st_last, t, nSt, rcnt, roff);
+  flush_run_counts<SPT, NT>(lrc, lro, B, st_last, t, nT, rloc, roff, ttot);
   if (!WIDE && kor) lkfail = 1;
   __syncthreads();
   if (threadIdx.x == 0 && s0 > base) publish(s0 - S, st_last);
@@ -423,18 +449,49 @@ __global__ __launch_bounds__(256) void k_c1_krange(const int64_t* __restrict__ k
   }
 }
 
-// Bucket bases from the scanned run counts: bb[b] = rpos[b][0], bb[B] = the total.
-__global__ __launch_bounds__(256) void k_c1_bases(const uint32_t* __restrict__ rpos, int64_t nSt, int B,
-                                                  int64_t* __restrict__ bb) {
-  for (int b = threadIdx.x; b <= B; b += blockDim.x) bb[b] = (int64_t)rpos[(int64_t)b * nSt];
+// Each tile's base in its bucket and each bucket's total: workgroup b scans bucket b's nT tile
+// totals (exclusive, bucket-relative) into tbase[b][0 .. nT), the total into tbase[b][nT].  No
+// workgroup waits for another.
+__global__ __launch_bounds__(1024) void k_c1_runpos(const uint32_t* __restrict__ ttot, int64_t nT,
+                                                    uint32_t* __restrict__ tbase) {
+  __shared__ uint32_t wsum[16];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t* in = ttot + (int64_t)blockIdx.x * nT;
+  uint32_t* out = tbase + (int64_t)blockIdx.x * (nT + 1);
+  uint32_t carry = 0u;
+  for (int64_t t0 = 0; t0 < nT; t0 += 1024) {  // uniform across the block: barriers inside
+    const int64_t t = t0 + threadIdx.x;
+    const uint32_t c = t < nT ? in[t] : 0u;
+    uint32_t incl = c;
+    for (int off = 1; off < 64; off <<= 1) {
+      const uint32_t y = __shfl_up(incl, off, 64);
+      if (lane >= off) incl += y;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0u, tot = 0u;
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+      before += k < wave ? wsum[k] : 0u;
+      tot += wsum[k];
+    }
+    if (t < nT) out[t] = carry + before + incl - c;
+    carry += tot;
+    __syncthreads();  // wsum is rewritten by the next round
+  }
+  if (threadIdx.x == 0) out[nT] = carry;
 }
 
 // Refine work item w → its bucket (cstart), its first step s0 and run count R (cinfo[2w],
-// [2w + 1]): one thread per item, binary searches over cstart and the bucket's scanned run
-// positions — so a refine workgroup starts with one round of table loads, not the searches.
-__global__ __launch_bounds__(256) void k_c1_chunks(const int* __restrict__ cstart, int B, const int64_t* __restrict__ bb,
-                                                   const uint32_t* __restrict__ rpos, int64_t nSt, int ch,
-                                                   const int64_t* __restrict__ ci, uint32_t* __restrict__ cinfo) {
+// [2w + 1]): one thread per item, binary searches over cstart and the bucket's run positions —
+// first the tile (over the nT tile bases), then the step inside it (over its 2^sh places) — so a
+// refine workgroup starts with one round of table loads, not the searches.  Positions are relative
+// to the bucket's first record.  Empty runs share their position with the next run: s0 is the
+// LAST step starting at or before the chunk, the end the FIRST step starting at or past its end.
+__global__ __launch_bounds__(256) void k_c1_chunks(const int* __restrict__ cstart, int B,
+                                                   const uint32_t* __restrict__ tbase, const uint16_t* __restrict__ rloc,
+                                                   int64_t nT, int sh, int ch, const int64_t* __restrict__ ci,
+                                                   uint32_t* __restrict__ cinfo) {
   if (ci_ld(ci, CI_GATE) == 0) return;
   const int w = blockIdx.x * blockDim.x + threadIdx.x;
   if (w >= (int)ci_ld(ci, CI_NCHUNK)) return;
@@ -445,35 +502,51 @@ __global__ __launch_bounds__(256) void k_c1_chunks(const int* __restrict__ cstar
     else e = m;
   }
   const int b = a;
-  const int64_t lo = bb[b] + (int64_t)(w - cstart[b]) * ch;
-  const int64_t len = bb[b + 1] - lo < ch ? bb[b + 1] - lo : ch;
-  const uint32_t* rp = rpos + (int64_t)b * nSt;
-  int64_t sa = 0, se = nSt;  // s0: the last step whose run starts at or before lo
-  while (se - sa > 1) {
-    const int64_t m = (sa + se) >> 1;
-    if ((int64_t)rp[m] <= lo) sa = m;
-    else se = m;
+  const int64_t nSt = nT << sh, spt = (int64_t)1 << sh;
+  const uint32_t* tb = tbase + (int64_t)b * (nT + 1);
+  const uint16_t* rl = rloc + (int64_t)b * nSt;
+  const int64_t lo = (int64_t)(w - cstart[b]) * ch, blen = (int64_t)tb[nT];
+  const int64_t hi = blen - lo < ch ? blen : lo + ch;
+  // s0 (sa): the last step whose run starts at or before lo.  The end: the first step after s0
+  // whose run starts at or past the chunk's end (or nSt), one past sl, the last step starting
+  // before it.  The two searches advance together, so their loads overlap: first the tiles (tb[0]
+  // = 0 passes both tests), then the 2^sh steps of each one's tile (whose first place is 0).
+  int64_t t0 = 0, e0 = nT, t1 = 0, e1 = nT;
+  while (e0 - t0 > 1 || e1 - t1 > 1) {
+    const int64_t m0 = (t0 + e0) >> 1, m1 = (t1 + e1) >> 1;  // (a finished search reloads its answer)
+    const int64_t p0 = (int64_t)tb[m0], p1 = (int64_t)tb[m1];
+    if (e0 - t0 > 1) {
+      if (p0 <= lo) t0 = m0;
+      else e0 = m0;
+    }
+    if (e1 - t1 > 1) {
+      if (p1 < hi) t1 = m1;
+      else e1 = m1;
+    }
   }
-  int64_t ta = sa, te = nSt;  // the first step after s0 whose run starts at or past lo + len (or nSt)
-  while (te - ta > 1) {
-    const int64_t m = (ta + te) >> 1;
-    if ((int64_t)rp[m] < lo + len) ta = m;
-    else te = m;
+  const int64_t b0 = (int64_t)tb[t0], b1 = (int64_t)tb[t1];
+  int64_t sa = t0 << sh, sl = t1 << sh;
+  for (int64_t half = spt >> 1; half > 0; half >>= 1) {
+    const int64_t q0 = b0 + (int64_t)rl[sa + half], q1 = b1 + (int64_t)rl[sl + half];
+    if (q0 <= lo) sa += half;
+    if (q1 < hi) sl += half;
   }
   cinfo[2 * w] = (uint32_t)sa;
-  cinfo[2 * w + 1] = (uint32_t)(te - sa);
+  cinfo[2 * w + 1] = (uint32_t)(sl + 1 - sa);
 }
 
 // The chunk's source positions: map[j] = where the chunk's record j lies in the step runs (u32 per
 // record, in the refine's not yet used stage).  One thread per run of the chunk (cinfo): one round
-// of loads of its position / end / step offset, then the run's slice of the map.
-__device__ __forceinline__ void chunk_map(const uint32_t* __restrict__ rp, const uint16_t* __restrict__ ro,
+// of loads of its position / end / step offset, then the run's slice of the map.  lo: the chunk's
+// first record, relative to the bucket's (as the run positions are).
+__device__ __forceinline__ void chunk_map(const uint32_t* __restrict__ tb, const uint16_t* __restrict__ rl,
+                                          const uint16_t* __restrict__ ro, int64_t nSt, int sh,
                                           const uint32_t* __restrict__ cinfo, int w, int64_t S, int64_t lo, int len,
                                           uint32_t* map) {
   const int64_t s0 = cinfo[2 * w];
   const int R = (int)cinfo[2 * w + 1];
   for (int k = threadIdx.x; k < R; k += blockDim.x) {
-    const int64_t s = s0 + k, p = (int64_t)rp[s], pe = (int64_t)rp[s + 1];  // rp[nSt] = the next bucket's start
+    const int64_t s = s0 + k, p = run_pos(tb, rl, nSt, sh, s), pe = run_pos(tb, rl, nSt, sh, s + 1);
     const int64_t a = p > lo ? p : lo, e = pe < lo + len ? pe : lo + len;
     const uint32_t src = (uint32_t)(s * S + (int64_t)ro[s] + (a - p));
     for (int64_t x = a; x < e; x++) map[x - lo] = src + (uint32_t)(x - a);
@@ -488,19 +561,28 @@ __device__ __forceinline__ void chunk_map(const uint32_t* __restrict__ rp, const
 // test at step granularity; S/StreamAggregateBuilder.java:272-277 for the grace).
 // Accepted: publish the stream time, the window range (k_part_wrange's rules, resident rows
 // included), the identity width and the refine's chunk list (cstart); reset the counters the
-// merge and commit use.  Declined: nothing persistent is touched.
+// merge and commit use, and write the push's statistics (the tiles' counters tpart, summed:
+// ctr[CTR_TILE ..], what k_part_stats computes on the general path).  Declined: nothing persistent
+// is touched.  Either way the bucket bases bb[0 .. B] (scratch of this push) from the bucket
+// totals tbase[b][nT] (k_c1_runpos).
 __global__ __launch_bounds__(1024) void k_c1_check(
-    const int64_t* __restrict__ tilestat, int64_t nT, int64_t size, int64_t adv, FastDiv fd, int64_t grace,
-    int64_t close0, int fresh, int log2B, int log2P, int wide, int ch, int kbmax, int pbits,
-    const int64_t* __restrict__ bb, int* __restrict__ cstart,
+    const int64_t* __restrict__ tilestat, const int64_t* __restrict__ tpart, int64_t nT, int64_t size, int64_t adv,
+    FastDiv fd, int64_t grace, int64_t close0, int fresh, int log2B, int log2P, int wide, int ch, int kbmax, int pbits,
+    const uint32_t* __restrict__ tbase, int64_t* __restrict__ bb, int* __restrict__ cstart,
     int64_t* __restrict__ ci, int64_t* __restrict__ stream_time, int64_t* __restrict__ res,
     unsigned long long* __restrict__ ctr, unsigned long long* __restrict__ closed_ctr, unsigned long long closed_n) {
   __shared__ int64_t wmx[16];
-  __shared__ int64_t red[4][16];
+  __shared__ int64_t red[2][16];
+  __shared__ unsigned long long lsum[T_NPART];  // the tiles' counters, summed
   __shared__ int lslow;
-  __shared__ int lnch[512 + 1];
+  __shared__ int64_t wtot[8];  // per wave of the first B threads: the buckets' records,
+  __shared__ int wnch[8], wmxc[8];  // chunks and largest chunk count
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (threadIdx.x == 0) lslow = 0;
+  if (threadIdx.x < T_NPART) lsum[threadIdx.x] = 0ULL;
+  // thread b < B: bucket b's total (k_c1_runpos), in flight during the tile loops
+  const int B = 1 << log2B;
+  const uint32_t btot = (int)threadIdx.x < B ? tbase[(int64_t)threadIdx.x * (nT + 1) + nT] : 0u;
   const int64_t st0 = *stream_time;
   // thread j owns tiles [j K, (j + 1) K): their stream-time maximum, the block's exclusive prefix
   // of those (the stream time carried into each tile), then each tile's summary (k_c1_scatter)
@@ -516,6 +598,7 @@ __global__ __launch_bounds__(1024) void k_c1_check(
   const int64_t excl = __shfl_up(incl, 1, 64);
   int64_t run = lane == 0 ? pre : (excl > pre ? excl : pre);  // stream time before tile g0
   int64_t gmn = INT64_MAX, gmx = -1;
+  int64_t tsum[T_NPART] = {};  // the tiles' counters (k_c1_scatter), summed
   bool slow = false;
   for (int64_t g = g0; g < g1; g++) {
     const int64_t* t4 = tilestat + 4 * g;
@@ -526,6 +609,8 @@ __global__ __launch_bounds__(1024) void k_c1_check(
     }
     run = mx > run ? mx : run;
     gmx = mx > gmx ? mx : gmx;
+#pragma unroll
+    for (int k = 0; k < T_NPART; k++) tsum[k] += tpart[g * T_NPART + k];
   }
   if (slow) lslow = 1;
   for (int off = 32; off > 0; off >>= 1) {
@@ -533,25 +618,59 @@ __global__ __launch_bounds__(1024) void k_c1_check(
     gmn = a < gmn ? a : gmn;
     gmx = b > gmx ? b : gmx;
   }
+#pragma unroll
+  for (int k = 0; k < T_NPART; k++) tsum[k] = wave_sum(tsum[k]);
   if (lane == 0) {
     red[0][wave] = gmn;
     red[1][wave] = gmx;
+#pragma unroll
+    for (int k = 0; k < T_NPART; k++)
+      if (tsum[k]) atomicAdd(&lsum[k], (unsigned long long)tsum[k]);
   }
-  // chunks per bucket → cstart (exclusive prefix), largest bucket's chunk count
-  const int B = 1 << log2B;
-  for (int b = threadIdx.x; b < B; b += 1024) lnch[b] = (int)((bb[b + 1] - bb[b] + ch - 1) / ch);
+  // the buckets' totals → bucket bases, chunks per bucket → cstart: exclusive prefixes over the
+  // first B threads (B <= 512: waves 0 .. 7), each writing its own bucket's; the largest bucket's
+  // chunk count
+  const int nch = (int)((btot + (uint32_t)ch - 1u) / (uint32_t)ch);  // (btot < 2^31: no wrap)
+  int64_t itot = (int64_t)btot;
+  int inch = nch, mnch = nch;
+  for (int off = 1; off < 64; off <<= 1) {
+    const int64_t y = __shfl_up(itot, off, 64);
+    const int z = __shfl_up(inch, off, 64), q = __shfl_xor(mnch, off, 64);
+    if (lane >= off) {
+      itot += y;
+      inch += z;
+    }
+    mnch = q > mnch ? q : mnch;
+  }
+  if (lane == 63 && wave < 8) {
+    wtot[wave] = itot;
+    wnch[wave] = inch;
+    wmxc[wave] = mnch;
+  }
   __syncthreads();
+  if ((int)threadIdx.x < B) {
+    int64_t bt = 0;
+    int bn = 0;
+    for (int w = 0; w < wave; w++) {
+      bt += wtot[w];
+      bn += wnch[w];
+    }
+    bb[threadIdx.x] = bt + itot - (int64_t)btot;
+    cstart[threadIdx.x] = bn + inch - nch;
+  }
   if (threadIdx.x) return;
   for (int w = 0; w < 16; w++) {
     gmn = red[0][w] < gmn ? red[0][w] : gmn;
     gmx = red[1][w] > gmx ? red[1][w] : gmx;
   }
   int acc = 0, mxc = 0;
-  for (int b = 0; b < B; b++) {
-    cstart[b] = acc;
-    acc += lnch[b];
-    mxc = lnch[b] > mxc ? lnch[b] : mxc;
+  int64_t base = 0;
+  for (int w = 0; w < 8; w++) {  // (waves past the B threads hold zeros)
+    base += wtot[w];
+    acc += wnch[w];
+    mxc = wmxc[w] > mxc ? wmxc[w] : mxc;
   }
+  bb[B] = base;
   cstart[B] = acc;
   const int64_t kmin = ci_ld(ci, CI_KMIN), kmax = ci_ld(ci, CI_KMAX);
   const bool tfail = ci_ld(ci, CI_TFAIL) != 0, kfail = ci_ld(ci, CI_KFAIL) != 0;
@@ -615,6 +734,7 @@ __global__ __launch_bounds__(1024) void k_c1_check(
   res[0] = none ? INT64_MAX : lo;
   res[1] = none ? INT64_MIN : hi;
   ctr[CTR_ADDED] = ctr[CTR_FAILED] = ctr[CTR_NEED] = 0ULL;
+  for (int k = 0; k < T_NPART; k++) ctr[CTR_TILE + k] = lsum[k];
   if (closed_ctr) *closed_ctr = closed_n;
 }
 
@@ -628,8 +748,9 @@ template <int U, int NT, bool WIDE>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_c1_refine(
     const uint64_t* __restrict__ srcA, const int64_t* __restrict__ bb, const int* __restrict__ cstart, int log2B,
     int log2P, int fbits, uint64_t* __restrict__ srec, uint16_t* __restrict__ seg, const int64_t* __restrict__ ci,
-    const uint32_t* __restrict__ srcAT, uint32_t* __restrict__ srecT, const uint32_t* __restrict__ rpos,
-    const uint16_t* __restrict__ roff, int64_t nSt, int64_t S, const uint32_t* __restrict__ cinfo) {
+    const uint32_t* __restrict__ srcAT, uint32_t* __restrict__ srecT, const uint32_t* __restrict__ tbase,
+    const uint16_t* __restrict__ rloc, const uint16_t* __restrict__ roff, int64_t nT, int sh, int64_t S,
+    const uint32_t* __restrict__ cinfo) {
   if (ci_ld(ci, CI_GATE) == 0) return;
   const int w = blockIdx.x;
   if (w >= (int)ci_ld(ci, CI_NCHUNK)) return;
@@ -656,9 +777,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
   const uint64_t kshift = WIDE ? 0 : (uint64_t)ci_ld(ci, CI_KSHIFT) << 32;  // records hold key - kb
   const int shift = 64 - log2P;
   // where the chunk's records lie in the step runs (a map in the not yet used stage)
-  const uint32_t* rp = rpos + (int64_t)b * nSt;
-  const uint16_t* ro = roff + (int64_t)b * nSt;
-  chunk_map(rp, ro, cinfo, w, S, lo, len, (uint32_t*)stage);
+  const int64_t nSt = nT << sh;
+  chunk_map(tbase + (int64_t)b * (nT + 1), rloc + (int64_t)b * nSt, roff + (int64_t)b * nSt, nSt, sh, cinfo, w, S,
+            lo - bb[b], len, (uint32_t*)stage);
   uint64_t r[U];
   uint32_t f[U], rank[U], t32[U];
 #pragma unroll
@@ -983,7 +1104,7 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
     uint32_t p;
     int sbits, sub, nseg, segb;  // segb: log2 of the records per segment-lookup block
     uint32_t rn;                 // records (< 2^31)
-    uint32_t bb0;                // the bucket's first record in srec (k_c1_bases: a u32 scan's value);
+    uint32_t bb0;                // the bucket's first record in srec (k_c1_check: a sum of u32 totals);
                                  // the segment bases are relative to it
     int64_t nrow;
     bool isel;
@@ -1506,8 +1627,8 @@ struct C1VCol {
 template <int U, int NT, bool ST, bool ROWS>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_c1v_scatter(
     const int64_t* __restrict__ keys, const int64_t* __restrict__ ts, const uint8_t* __restrict__ kv,
-    const uint8_t* __restrict__ rv, C1VCol vc, RowsIn ri, int64_t n, int64_t nT, int log2B, uint32_t* __restrict__ rcnt,
-    uint16_t* __restrict__ roff, int64_t nSt, ulonglong2* __restrict__ srec, int64_t* __restrict__ tilestat,
+    const uint8_t* __restrict__ rv, C1VCol vc, RowsIn ri, int64_t n, int64_t nT, int log2B, uint16_t* __restrict__ rloc,
+    uint16_t* __restrict__ roff, uint32_t* __restrict__ ttot, ulonglong2* __restrict__ srec, int64_t* __restrict__ tilestat,
     int64_t* __restrict__ tpart, int64_t* __restrict__ ci, const int64_t* __restrict__ st_at, int64_t size, int64_t adv,
     FastDiv fd, int hop, int64_t grace, const int64_t* __restrict__ stream_time, int64_t kb_in, int has_kb) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1656,7 +1777,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
     }
     if (threadIdx.x == 0 && st > 0) publish(s0 - S, st - 1);
   }
-  flush_run_counts<SPT, NT>(lrc, lro, B, st_last, t, nSt, rcnt, roff);
+  flush_run_counts<SPT, NT>(lrc, lro, B, st_last, t, nT, rloc, roff, ttot);
   if (kor) lkfail = 1;
   __syncthreads();
   if (threadIdx.x == 0 && s0 > base) publish(s0 - S, st_last);
@@ -1697,8 +1818,8 @@ template <int U, int NT>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_c1v_refine(
     const ulonglong2* __restrict__ srcA, const int64_t* __restrict__ bb, const int* __restrict__ cstart, int log2B,
     int log2P, int fbits, ulonglong2* __restrict__ srec, uint16_t* __restrict__ seg, const int64_t* __restrict__ ci,
-    const uint32_t* __restrict__ rpos, const uint16_t* __restrict__ roff, int64_t nSt, int64_t S,
-    const uint32_t* __restrict__ cinfo) {
+    const uint32_t* __restrict__ tbase, const uint16_t* __restrict__ rloc, const uint16_t* __restrict__ roff,
+    int64_t nT, int sh, int64_t S, const uint32_t* __restrict__ cinfo) {
   if (ci_ld(ci, CI_GATE) == 0) return;
   const int w = blockIdx.x;
   if (w >= (int)ci_ld(ci, CI_NCHUNK)) return;
@@ -1726,9 +1847,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void k_
   const uint64_t kshift = (uint64_t)ci_ld(ci, CI_KSHIFT) << 32;  // records hold key - kb
   const int shift = 64 - log2P;
   // where the chunk's records lie in the step runs (a map in the not yet used stage)
-  const uint32_t* rp = rpos + (int64_t)b * nSt;
-  const uint16_t* ro = roff + (int64_t)b * nSt;
-  chunk_map(rp, ro, cinfo, w, S, lo, len, (uint32_t*)stage);
+  const int64_t nSt = nT << sh;
+  chunk_map(tbase + (int64_t)b * (nT + 1), rloc + (int64_t)b * nSt, roff + (int64_t)b * nSt, nSt, sh, cinfo, w, S,
+            lo - bb[b], len, (uint32_t*)stage);
   ulonglong2 r[U];
   uint32_t f[U], rank[U];
 #pragma unroll
@@ -2656,8 +2777,9 @@ struct C1Geo {
   int* cstart;
   uint16_t* seg;
   uint32_t *srecAT, *srecT;  // the WIDE records' ts words (12 B/record in all)
-  uint32_t *rc, *rp;
-  uint16_t* ro;
+  int sh;             // log2 of the steps per tile
+  uint32_t *tt, *tb;  // run positions: [bucket][tile] totals, [bucket][tile + 1] bases (k_c1_runpos)
+  uint16_t *rl, *ro;  // [bucket][step]: the run's place within its tile, the bucket's offset in the step's run
   int64_t adv, close0;
   FastDiv fd;
 };
@@ -2691,8 +2813,11 @@ static khip_status c1_prepare(khip_agg* a, int64_t n, const C1In& in, C1Geo* g) 
   g->nSt = g->nT * (C1_TILE / g->S);  // (runs per bucket)
   g->nchunk_max = ceil_div(n, g->CH) + g->B;
   const int64_t B = g->B, nSt = g->nSt, nT = g->nT;
-  KHIP_TRY(s.c1rc.ensure((size_t)B * nSt * 4));
-  KHIP_TRY(s.c1rp.ensure(((size_t)B * nSt + 1) * 4));
+  static_assert(C1_TILE / (C1V_UV * C1_NT) == 32 && C1_TILE / (8 * C1_NT) == 16, "steps per tile");
+  g->sh = g->val ? 5 : 4;
+  KHIP_TRY(s.c1rc.ensure((size_t)B * nT * 4));
+  KHIP_TRY(s.c1rp.ensure((size_t)B * (nT + 1) * 4));
+  KHIP_TRY(s.c1rl.ensure((size_t)B * nSt * 2));
   KHIP_TRY(s.c1ro.ensure((size_t)B * nSt * 2));
   KHIP_TRY(s.c1bb.ensure((size_t)(B + 1) * 8));
   g->seg_bytes = ((size_t)g->nchunk_max * (g->F + 1) * 2 + 255) & ~(size_t)255;  // cstart 256-B aligned
@@ -2708,14 +2833,7 @@ static khip_status c1_prepare(khip_agg* a, int64_t n, const C1In& in, C1Geo* g) 
   }
   KHIP_TRY(s.srec.ensure((size_t)(n + 1) * 16));  // (s.rw >= 2: no-ops)
   KHIP_TRY(s.srecA.ensure((size_t)(n + 1) * std::max(s.rw, 2) * 8));
-  if (!s.c1info.p) {
-    KHIP_TRY(s.c1info.ensure(CI_N * 8));
-    int64_t init[CI_N] = {};
-    init[CI_KMIN] = INT64_MAX;
-    init[CI_KMAX] = INT64_MIN;
-    KHIP_TRY_HIP(hipMemcpy(s.c1info.p, init, sizeof(init), hipMemcpyHostToDevice));
-  }
-  g->ci = s.c1info.as<int64_t>();
+  g->ci = s.ctr.as<int64_t>() + CTR_ALLOC;  // the c1info block lies behind the counters (part_init)
 #ifdef KHIP_TUNING
   {
     const int64_t dbg = knob("KHIP_C1_DEBUG", 0);
@@ -2733,14 +2851,15 @@ static khip_status c1_prepare(khip_agg* a, int64_t n, const C1In& in, C1Geo* g) 
   g->wide = !g->val && s.c1_wide;
   g->srecAT = (uint32_t*)(s.srecA.as<uint64_t>() + n + 1);
   g->srecT = (uint32_t*)(s.srec.as<uint64_t>() + n + 1);
-  g->rc = s.c1rc.as<uint32_t>();
-  g->rp = s.c1rp.as<uint32_t>();
+  g->tt = s.c1rc.as<uint32_t>();
+  g->tb = s.c1rp.as<uint32_t>();
+  g->rl = s.c1rl.as<uint16_t>();
   g->ro = s.c1ro.as<uint16_t>();
   return KHIP_OK;
 }
 
 // 1. records → step runs (the key range, time base and bucket counts in the same read)
-// 2. each (bucket, step) run's place in its bucket's order; the bucket bases
+// 2. each tile's base in its buckets and the buckets' totals (k_c1_runpos)
 static khip_status c1_scatter(khip_agg* a, const C1In& in, const C1Geo& g) {
   PartState& s = a->part;
   ev_record_part(a, 0);
@@ -2757,7 +2876,7 @@ static khip_status c1_scatter(khip_agg* a, const C1In& in, const C1Geo& g) {
     const size_t lds = run_stage_lds(g.B, UV * C1_NT, 16, false) + run_cnt_lds(g.B, C1_TILE / (UV * C1_NT));
     if (lds > 64 * 1024) hipFuncSetAttribute((const void*)sk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(sk, dim3(g.nT), dim3(C1_NT), lds, a->stream, in.keys, in.ts, in.kv, in.rv, vc, ri, g.n, g.nT,
-                       g.log2B, g.rc, g.ro, g.nSt, (ulonglong2*)s.srecA.p, s.tilemax.as<int64_t>(),
+                       g.log2B, g.rl, g.ro, g.tt, (ulonglong2*)s.srecA.p, s.tilemax.as<int64_t>(),
                        s.tpart.as<int64_t>(), g.ci, st_at, a->desc.size_ms, g.adv, g.fd,
                        a->desc.size_ms != g.adv ? 1 : 0, a->grace, (const int64_t*)a->stream_time.as<int64_t>(),
                        s.c1_kbase, has_kb);
@@ -2768,14 +2887,13 @@ static khip_status c1_scatter(khip_agg* a, const C1In& in, const C1Geo& g) {
     const size_t lds = run_stage_lds(g.B, U * C1_NT, 8, g.wide) + run_cnt_lds(g.B, C1_TILE / (U * C1_NT));
     if (lds > 64 * 1024) hipFuncSetAttribute((const void*)sk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(sk, dim3(g.nT), dim3(C1_NT), lds, a->stream, in.keys, in.ts, in.kv, in.rv, g.n, g.nT, g.log2B,
-                       g.rc, g.ro, g.nSt, s.srecA.as<uint64_t>(), s.tilemax.as<int64_t>(), s.tpart.as<int64_t>(), g.ci,
+                       g.rl, g.ro, g.tt, s.srecA.as<uint64_t>(), s.tilemax.as<int64_t>(), s.tpart.as<int64_t>(), g.ci,
                        st_at, g.srecAT, a->desc.size_ms, g.adv, g.fd, a->grace,
                        (const int64_t*)a->stream_time.as<int64_t>(), s.c1_kbase, has_kb);
   }
   KHIP_TRY_HIP(hipGetLastError());
-  KHIP_TRY((ksort::scan_excl<uint32_t, uint32_t>(a->stream, s.c1scan, g.rc, g.rp, (int64_t)g.B * g.nSt, true, nullptr)));
-  hipLaunchKernelGGL(k_c1_bases, dim3(1), dim3(256), 0, a->stream, (const uint32_t*)g.rp, g.nSt, g.B,
-                     s.c1bb.as<int64_t>());
+  hipLaunchKernelGGL(k_c1_runpos, dim3(g.B), dim3(1024), 0, a->stream, (const uint32_t*)g.tt, g.nT, g.tb);
+  KHIP_TRY_HIP(hipGetLastError());
   ev_record_part(a, 1);
   return KHIP_OK;
 }
@@ -2789,7 +2907,7 @@ static khip_status c1_refine(khip_agg* a, const C1Geo& g) {
     hipFuncSetAttribute((const void*)rk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(rk, dim3((unsigned)g.nchunk_max), dim3(C1_NT), lds, a->stream, (const ulonglong2*)s.srecA.p,
                        s.c1bb.as<int64_t>(), g.cstart, g.log2B, s.log2P, g.fbits, (ulonglong2*)s.srec.p, g.seg, g.ci,
-                       (const uint32_t*)g.rp, (const uint16_t*)g.ro, g.nSt, g.S,
+                       (const uint32_t*)g.tb, (const uint16_t*)g.rl, (const uint16_t*)g.ro, g.nT, g.sh, g.S,
                        (const uint32_t*)s.c1ci.as<uint32_t>());
   } else {
     constexpr int U = C1_CH / C1_NT;
@@ -2798,27 +2916,28 @@ static khip_status c1_refine(khip_agg* a, const C1Geo& g) {
     if (lds > 64 * 1024) hipFuncSetAttribute((const void*)rk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(rk, dim3((unsigned)g.nchunk_max), dim3(C1_NT), lds, a->stream, s.srecA.as<uint64_t>(),
                        s.c1bb.as<int64_t>(), g.cstart, g.log2B, s.log2P, g.fbits, s.srec.as<uint64_t>(), g.seg, g.ci,
-                       (const uint32_t*)g.srecAT, g.srecT, (const uint32_t*)g.rp, (const uint16_t*)g.ro, g.nSt, g.S,
-                       (const uint32_t*)s.c1ci.as<uint32_t>());
+                       (const uint32_t*)g.srecAT, g.srecT, (const uint32_t*)g.tb, (const uint16_t*)g.rl,
+                       (const uint16_t*)g.ro, g.nT, g.sh, g.S, (const uint32_t*)s.c1ci.as<uint32_t>());
   }
   KHIP_TRY_HIP(hipGetLastError());
   return KHIP_OK;
 }
 
-// The record stages: scatter, scan, bases, check, chunks, refine.
+// The record stages: scatter, run positions, check, chunks, refine.
 static khip_status c1_records(khip_agg* a, const C1In& in, const C1Geo& g) {
   PartState& s = a->part;
   KHIP_TRY(c1_scatter(a, in, g));
-  // 4. accept or decline
-  hipLaunchKernelGGL(k_c1_check, dim3(1), dim3(1024), 0, a->stream, s.tilemax.as<int64_t>(), g.nT, a->desc.size_ms,
-                     g.adv, g.fd, a->grace, g.close0, s.res_fresh ? 1 : 0, g.log2B, s.log2P, g.wide ? 1 : 0, g.CH,
-                     g.val ? 31 : 32, g.panes ? 1 : 0, s.c1bb.as<int64_t>(), g.cstart, g.ci,
-                     a->stream_time.as<int64_t>(), s.res.as<int64_t>(), s.ctr.as<unsigned long long>(),
-                     s.closed_ctr.as<unsigned long long>(), (unsigned long long)s.closed_n);
+  // 4. accept or decline (and the bucket bases, the push's statistics)
+  hipLaunchKernelGGL(k_c1_check, dim3(1), dim3(1024), 0, a->stream, s.tilemax.as<int64_t>(),
+                     (const int64_t*)s.tpart.as<int64_t>(), g.nT, a->desc.size_ms, g.adv, g.fd, a->grace, g.close0,
+                     s.res_fresh ? 1 : 0, g.log2B, s.log2P, g.wide ? 1 : 0, g.CH, g.val ? 31 : 32, g.panes ? 1 : 0,
+                     (const uint32_t*)g.tb, s.c1bb.as<int64_t>(), g.cstart, g.ci, a->stream_time.as<int64_t>(),
+                     s.res.as<int64_t>(), s.ctr.as<unsigned long long>(), s.closed_ctr.as<unsigned long long>(),
+                     (unsigned long long)s.closed_n);
   // 5. refine: each chunk's step runs (k_c1_chunks), chunks → partition-sorted, segment table
   KHIP_TRY(s.c1ci.ensure((size_t)g.nchunk_max * 8));
   hipLaunchKernelGGL(k_c1_chunks, dim3((unsigned)ceil_div(g.nchunk_max, 256)), dim3(256), 0, a->stream,
-                     (const int*)g.cstart, g.B, (const int64_t*)s.c1bb.as<int64_t>(), (const uint32_t*)g.rp, g.nSt, g.CH,
+                     (const int*)g.cstart, g.B, (const uint32_t*)g.tb, (const uint16_t*)g.rl, g.nT, g.sh, g.CH,
                      (const int64_t*)g.ci, s.c1ci.as<uint32_t>());
   KHIP_TRY(c1_refine(a, g));
   ev_record_part(a, 2);
@@ -2949,12 +3068,12 @@ static khip_status c1_declined_next(khip_agg* a, const C1In& in, const C1Geo& g,
   bool go_wide = !g.val && hci[CI_REASON] == 1;  // only the record format was wrong
   if (hci[CI_REASON] == 2 && !kretried) {  // a key outside the field above kb: the true range
     long long kr[2] = {INT64_MIN, INT64_MIN};
-    KHIP_TRY(s.c1scan.ensure(16));
-    KHIP_TRY_HIP(hipMemcpyAsync(s.c1scan.p, kr, 16, hipMemcpyHostToDevice, a->stream));
+    KHIP_TRY(s.c1kr.ensure(16));
+    KHIP_TRY_HIP(hipMemcpyAsync(s.c1kr.p, kr, 16, hipMemcpyHostToDevice, a->stream));
     hipLaunchKernelGGL(k_c1_krange, dim3((unsigned)std::min<int64_t>(ceil_div(g.n, 256), 2048)), dim3(256), 0,
                        a->stream, in.rows ? (const int64_t*)in.rows->rows : in.keys,
-                       in.rows ? (int64_t)in.rows->rw : 1, g.n, s.c1scan.as<long long>());
-    KHIP_TRY_HIP(hipMemcpyAsync(kr, s.c1scan.p, 16, hipMemcpyDeviceToHost, a->stream));
+                       in.rows ? (int64_t)in.rows->rw : 1, g.n, s.c1kr.as<long long>());
+    KHIP_TRY_HIP(hipMemcpyAsync(kr, s.c1kr.p, 16, hipMemcpyDeviceToHost, a->stream));
     KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
     const int64_t kmin = (int64_t)~(uint64_t)kr[0], kmax = (int64_t)kr[1];
     if ((uint64_t)kmax - (uint64_t)kmin < (1ULL << (g.val ? 31 : 32)) - 1) {  // again with kb = kmin
@@ -3020,12 +3139,11 @@ khip_status c1_push(khip_agg* a, int64_t n, const C1In& in, int64_t* tot, bool* 
       const uint32_t* wk = (pass == 0 && !subs0) ? nullptr : s.work.as<uint32_t>();
       const int64_t nwork = wk ? (int64_t)r.work.size() : g.P;
       KHIP_TRY(c1_launch_merge(a, g, m, pass, wk, nwork, dbg));
+      // one copy back per pass: the counters (with them the closed store's rows after this pass,
+      // CTR_CLOSED: closed rows leave in the pass that writes their item) and, on pass 0, the c1info
+      // block behind them
       KHIP_TRY(part_pass_commit(a, pass, r, pass == 0 ? (const int64_t*)g.ci : (const int64_t*)nullptr,
-                                s.prn.as<uint32_t>(), s.closed_ctr.as<unsigned long long>(), g.nT));
-      if (pass == 0) KHIP_TRY_HIP(hipMemcpyAsync(pi->c1info, g.ci, CI_N * 8, hipMemcpyDeviceToHost, a->stream));
-      // the closed store's rows after this pass (closed rows leave in the pass that writes their
-      // item): read with the counters, no second round trip
-      KHIP_TRY_HIP(hipMemcpyAsync(&pi->closed_n, s.closed_ctr.p, 8, hipMemcpyDeviceToHost, a->stream));
+                                s.prn.as<uint32_t>(), s.closed_ctr.as<unsigned long long>(), g.nT, true));
       KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
       if (pass == 0 && pi->c1info[CI_GATE] == 0) {  // declined: nothing was written
         KHIP_TRY(c1_declined_next(a, in, g, kretried, &next));
@@ -3058,7 +3176,7 @@ khip_status c1_push(khip_agg* a, int64_t n, const C1In& in, int64_t* tot, bool* 
                 "[c1 trace] val=%d P=%d cmax=%lld log2H=%d pass=%d items=%lld sub_items=%lld failed=%llu fail_table=%lld "
                 "fail_region=%lld closed_before=%lld closed_after=%llu\n",
                 g.val ? 1 : 0, g.P, (long long)s.cmax, g.val ? m.v_log2H : m.log2H, pass, (long long)nwork,
-                (long long)nsub, c2[CTR_FAILED], (long long)ft, (long long)fr, (long long)s.closed_n, pi->closed_n);
+                (long long)nsub, c2[CTR_FAILED], (long long)ft, (long long)fr, (long long)s.closed_n, c2[CTR_CLOSED]);
       }
 #endif
       if (c2[CTR_FAILED] == 0) break;
@@ -3080,8 +3198,8 @@ khip_status c1_push(khip_agg* a, int64_t n, const C1In& in, int64_t* tot, bool* 
     retry_learn(s.c1psbits, r);
     s.res_fresh = false;
     s.last_c1 = true;
-    // the closed store's rows after every pass (read with the last pass's counters)
-    part_push_epilogue(a, (int64_t)pi->closed_n, added_total, tot);
+    // the closed store's rows after every pass (k_part_commit refreshes CTR_CLOSED on each)
+    part_push_epilogue(a, (int64_t)c2[CTR_CLOSED], added_total, tot);
     return KHIP_OK;
   }
 }

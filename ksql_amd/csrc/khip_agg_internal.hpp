@@ -644,16 +644,18 @@ struct InitWords {
 // The partitioned engine's pinned block (PartState::pinfo): what a push copies back from the device
 // and the words it stages for the device.  A staging word shares no storage with anything a
 // device-to-host copy writes.
-constexpr int PINFO_CTR_WORDS = 13, PINFO_CI_WORDS = 24;  // = CTR_COPIED, CI_N (khip_part.hpp asserts it)
+constexpr int PINFO_CTR_WORDS = 16, PINFO_CI_WORDS = 24;  // = CTR_ALLOC, CI_N (khip_part.hpp asserts it)
 struct PushInfo {
   // device to host
   // k_part_wrange writes nine words; the host copies the first six (window-index base, identity
   // fits, event-time min / max, merge accepted, time base) and part_push reads wr[4] after the
   // pass-0 sync.  wr[6..9) (R8 key base, rowtime-delta bits, half-range flag) are for kernels only.
   int64_t wr[6];
+  // ctr and c1info mirror the device allocation PartState::ctr (the counter block, the c1info block
+  // behind it): pass 0 of a pipeline push copies both in one transfer, every other pass the
+  // first CTR_COPIED words
   unsigned long long ctr[PINFO_CTR_WORDS];   // the counter block after a pass (CTR_*)
   int64_t c1info[PINFO_CI_WORDS];            // c1_push: the pipeline's c1info after pass 0 (CI_*)
-  unsigned long long closed_n;               // c1_push: the closed store's rows after a pass
   // host to device
   int64_t seed_st;                           // khip_agg.hip: the stream time before the batch
   int64_t sup_after;                         // khip_agg.hip: the supplied stream time after it
@@ -714,9 +716,12 @@ struct PartState {
   // COUNT(*) pipeline (khip_agg_c1.hip): bucket bases, the
   // refine's per-chunk partition offsets, records of each partition in the last push (prn), and
   // whether the last push took that pipeline (k_part_chg then reads prn instead of pbase)
-  DevBuf c1bb, c1seg, c1info, prn;
-  DevBuf c1rc, c1rp, c1ro, c1scan, c1ci;  // step-run layout: [bucket][step] counts, their scan, step
-                                          // offsets; per refine chunk its first step and run count
+  DevBuf c1bb, c1seg, prn;  // (the c1info block lies behind the counters, in ctr)
+  // step-run layout: [bucket][tile] totals (c1rc), their per-bucket scan ([bucket][tile + 1], c1rp),
+  // [bucket][step] the run's place within its tile (c1rl) and the bucket's offset in the step's
+  // run (c1ro); per refine chunk its first step and run count (c1ci)
+  DevBuf c1rc, c1rp, c1rl, c1ro, c1ci;
+  DevBuf c1kr;  // a declined push's exact key range (k_c1_krange)
   int64_t c1_kbase = 0;             // key base for the next push's records (valid when c1_kb_valid)
   bool c1_kb_valid = false;
   int64_t c1_wide_n = 0;            // pushes with wide records (compact ones are tried every 64th)

@@ -3318,9 +3318,17 @@ __global__ __launch_bounds__(256) void k_part_commit(const int64_t* __restrict__
                                                      const uint8_t* __restrict__ fail,
                                                      unsigned long long* __restrict__ out /* [new groups, failed] */,
                                                      unsigned long long* __restrict__ hcnt,
-                                                     unsigned long long* __restrict__ hnew) {
+                                                     unsigned long long* __restrict__ hnew,
+                                                     const unsigned long long* __restrict__ closed_n,
+                                                     const int64_t* __restrict__ stream_time) {
   if (gate && gate[4] == 0) return;
   const int k = blockIdx.x * 256 + threadIdx.x;
+  // the pipelines' pushes (stream_time set): the closed store's rows after this pass's merge and
+  // the stream time, with the pass's counters (the general path: k_part_stats)
+  if (k == 0 && stream_time) {
+    out[CTR_CLOSED] = closed_n ? *closed_n : 0ULL;
+    out[CTR_STREAM_TIME] = (unsigned long long)*stream_time;
+  }
   int64_t added = 0, failed = 0, hdelta = 0;
   if (plist ? k < nlist : k < P) {
     const uint32_t p = plist ? plist[k] : (uint32_t)k;
@@ -3620,7 +3628,15 @@ khip_status part_init(khip_agg* a, int64_t hint) {
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, a->device) == hipSuccess && ncu > 0)
       s.n_cu = ncu;
   }
-  KHIP_TRY(s.ctr.ensure(CTR_ALLOC * 8));
+  // the counter block and, behind it, the pipelines' c1info block: one allocation, so that a
+  // pipeline push reads both back in one copy (PushInfo::ctr, c1info)
+  KHIP_TRY(s.ctr.ensure((CTR_ALLOC + CI_N) * 8));
+  {
+    int64_t init[CI_N] = {};
+    init[CI_KMIN] = INT64_MAX;  // the scatters' atomics start here; k_c1_check resets them after every push
+    init[CI_KMAX] = INT64_MIN;
+    KHIP_TRY_HIP(hipMemcpy(s.ctr.as<int64_t>() + CTR_ALLOC, init, sizeof(init), hipMemcpyHostToDevice));
+  }
   KHIP_TRY(s.hcnt.ensure(s.P * 8));
   KHIP_TRY(s.hnew.ensure(s.P * 8));
   KHIP_TRY(s.pinfo.ensure(sizeof(PushInfo)));
@@ -3645,7 +3661,7 @@ void part_release(khip_agg* a) {
   DevBuf* bufs[] = {&s.hcnt, &s.hnew, &s.srecA, &s.hcoarse, &s.scan_tmpB, &s.RB, &s.wr, &s.res, &s.closed, &s.closed_ctr, &s.closed2, &s.pctr, &s.buf[0], &s.buf[1], &s.sel, &s.cnt, &s.newcnt, &s.fail, &s.hist,
                     &s.tilemax, &s.tilemin, &s.tilekr,
                     &s.tileprefix, &s.tpart, &s.scan_tmp, &s.srec, &s.work,
-                    &s.c1rc, &s.c1rp, &s.c1ro, &s.c1scan, &s.c1ci, &s.c1bb, &s.c1seg, &s.c1info, &s.prn, &s.c1vq,
+                    &s.c1rc, &s.c1rp, &s.c1rl, &s.c1ro, &s.c1kr, &s.c1ci, &s.c1bb, &s.c1seg, &s.prn, &s.c1vq,
                     &s.pbase, &s.ctr, &s.counts};
   for (DevBuf* b : bufs) b->release();
 }
@@ -3876,24 +3892,29 @@ void part_push_epilogue(khip_agg* a, int64_t closed_now, int64_t added, int64_t*
 
 // A pass's tail, after its aggregate / merge kernel: commit (gate: the device's go-ahead word block on
 // pass 0, prn: the pipelines' records per partition, both may be null), the push's statistics
-// after pass 0 (evictions only happen there; closed_ctr null: unwindowed), the counters → host.
-// The caller adds its own copies and synchronises the stream.
+// (closed_ctr null: unwindowed), the counters → host.  The general path: k_part_stats after pass 0
+// (evictions only happen there).  pipeline (c1_push): k_c1_check summed the tiles' counters,
+// k_part_commit itself writes the closed rows and the stream time on every pass, and pass 0's copy
+// takes the c1info block behind the counters with it.  The caller synchronises the stream.
 khip_status part_pass_commit(khip_agg* a, int pass, const RetryPlan& r, const int64_t* gate, const uint32_t* prn,
-                             const unsigned long long* closed_ctr, int64_t nT) {
+                             const unsigned long long* closed_ctr, int64_t nT, bool pipeline) {
   PartState& s = a->part;
   const int P = (int)s.P, nl = pass == 0 ? P : (int)r.plist.size();
   hipLaunchKernelGGL(k_part_commit, dim3(ceil_div(std::max(nl, 1), 256)), dim3(256), 0, a->stream, gate, P,
                      s.pbase.as<int64_t>(), prn, pass == 0 ? nullptr : s.work.as<uint32_t>() + r.work.size(), nl,
                      s.sel.as<uint8_t>(), s.cnt.as<int64_t>(), s.newcnt.as<unsigned long long>(),
                      s.fail.as<uint8_t>(), s.ctr.as<unsigned long long>(), s.hcnt.as<unsigned long long>(),
-                     s.hnew.as<unsigned long long>());
+                     s.hnew.as<unsigned long long>(), closed_ctr,
+                     pipeline ? (const int64_t*)a->stream_time.as<int64_t>() : (const int64_t*)nullptr);
   KHIP_TRY_HIP(hipGetLastError());
   if (pass == 0) {
     ev_record_part(a, 3);
-    hipLaunchKernelGGL(k_part_stats, dim3(1), dim3(256), 0, a->stream, s.tpart.as<int64_t>(), nT, closed_ctr,
-                       a->stream_time.as<int64_t>(), s.ctr.as<unsigned long long>());
+    if (!pipeline)
+      hipLaunchKernelGGL(k_part_stats, dim3(1), dim3(256), 0, a->stream, s.tpart.as<int64_t>(), nT, closed_ctr,
+                         a->stream_time.as<int64_t>(), s.ctr.as<unsigned long long>());
   }
-  KHIP_TRY_HIP(hipMemcpyAsync(s.info()->ctr, s.ctr.p, CTR_COPIED * 8, hipMemcpyDeviceToHost, a->stream));
+  const size_t words = pipeline && pass == 0 ? CTR_ALLOC + CI_N : CTR_COPIED;
+  KHIP_TRY_HIP(hipMemcpyAsync(s.info()->ctr, s.ctr.p, words * 8, hipMemcpyDeviceToHost, a->stream));
   return KHIP_OK;
 }
 
@@ -4327,7 +4348,7 @@ static khip_status part_run_pass(khip_agg* a, const PartGeo& g, PartAggQ& k, con
   part_launch_agg(a, g, k, merge, pass, wk, *nwork, *dbg);
   KHIP_TRY(part_pass_commit(a, pass, r, (merge && pass == 0) ? s.wr.as<int64_t>() : (const int64_t*)nullptr, nullptr,
                             a->windowed ? s.closed_ctr.as<unsigned long long>() : (const unsigned long long*)nullptr,
-                            g.nT));
+                            g.nT, false));
   KHIP_TRY_HIP(hipStreamSynchronize(a->stream));
   return KHIP_OK;
 }

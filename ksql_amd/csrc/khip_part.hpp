@@ -14,17 +14,17 @@ enum {
   CTR_ADDED = 0,                   // groups added by the pass (k_part_commit)
   CTR_FAILED = 1,                  // partitions that failed the pass (k_part_commit)
   CTR_NEED = 2,                    // region rows the largest overflowing partition needed (| C1_FATAL)
-  CTR_TILE = 3,                    // [T_NPART] the tiles' counters, summed (k_part_stats)
+  CTR_TILE = 3,                    // [T_NPART] the tiles' counters, summed (k_part_stats; pipelines: k_c1_check)
   CTR_PER_PASS = CTR_TILE,         // the words before are cleared for every pass
-  CTR_CLOSED = CTR_TILE + T_NPART,  // closed rows (k_part_stats)
-  CTR_STREAM_TIME,                 // stream time after the push (k_part_stats)
+  CTR_CLOSED = CTR_TILE + T_NPART,  // closed rows (k_part_stats; pipelines: k_part_commit, every pass)
+  CTR_STREAM_TIME,                 // stream time after the push (as CTR_CLOSED)
   CTR_HAVING_LIVE,                 // live rows passing the query's HAVING (maintained: += new - old)
   CTR_HAVING_CLOSED,               // closed rows passing it
   CTR_COPIED,                      // words the host reads back
-  CTR_ALLOC = 16                   // words allocated (and zeroed by a reset)
+  CTR_ALLOC = 16                   // words of the block (zeroed by a reset); the c1info block follows it
 };
 static_assert(CTR_HAVING_LIVE == 11 && CTR_HAVING_CLOSED == 12, "the counter block's layout");
-static_assert(CTR_COPIED == PINFO_CTR_WORDS && CTR_COPIED <= CTR_ALLOC, "the counter copy fits its buffers");
+static_assert(CTR_ALLOC == PINFO_CTR_WORDS && CTR_COPIED <= CTR_ALLOC, "the counter copy fits its buffers");
 // in the CTR_NEED word: a reservation past the closed store's capacity
 constexpr unsigned long long C1_FATAL = 1ULL << 63;
 
@@ -54,6 +54,8 @@ enum {
   CI_N = 24
 };
 static_assert(CI_N == PINFO_CI_WORDS, "PushInfo holds a c1info copy");
+static_assert(offsetof(PushInfo, c1info) == offsetof(PushInfo, ctr) + CTR_ALLOC * 8,
+              "PushInfo mirrors the device's counter block + c1info block");
 
 // Key hash: its top log2P bits pick the partition; inside a partition the LDS slot and the
 // sub-pass of a (key, windowStart) group mix its low bits with ws (cheap 32-bit math).
@@ -227,7 +229,7 @@ khip_status part_plan_retry(khip_agg* a, RetryPlan& r, int pass, const std::vect
 void part_retry_trace_counts(const RetryPlan& r, bool listed, const std::vector<uint8_t>& host_fail, int64_t* nsub,
                              int64_t* fail_table, int64_t* fail_region);
 khip_status part_pass_commit(khip_agg* a, int pass, const RetryPlan& r, const int64_t* gate, const uint32_t* prn,
-                             const unsigned long long* closed_ctr, int64_t nT);
+                             const unsigned long long* closed_ctr, int64_t nT, bool pipeline);
 khip_status part_pass_failed(khip_agg* a, std::vector<uint8_t>* host_fail);
 void part_push_epilogue(khip_agg* a, int64_t closed_now, int64_t added, int64_t* tot);
 // khip_agg_c1.hip: the windowed COUNT(*) pipeline (declined = the general path must run)
@@ -248,6 +250,7 @@ __global__ void k_part_commit(const int64_t* __restrict__ gate, int P, const int
                               uint8_t* __restrict__ sel, int64_t* __restrict__ cnt,
                               unsigned long long* __restrict__ newcnt, const uint8_t* __restrict__ fail,
                               unsigned long long* __restrict__ out, unsigned long long* __restrict__ hcnt,
-                              unsigned long long* __restrict__ hnew);
+                              unsigned long long* __restrict__ hnew, const unsigned long long* __restrict__ closed_n,
+                              const int64_t* __restrict__ stream_time);
 
 }  // namespace khip

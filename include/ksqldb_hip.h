@@ -808,6 +808,7 @@ khip_status khip_comm_destroy(khip_comm* c);
  *              (connect/ConnectDataTranslator.java:290-318); a writer type the column's type does
  *              not accept (validateSchema :123-146: BIGINT ← int / long, INT ← int, DOUBLE ← float /
  *              double, STRING ← any primitive) fails every record; missing columns are NULL.
+ *   PROTOBUF / PROTOBUF_NOSR  see "PROTOBUF values (deserialization)" below.
  * A record that fails to deserialize is dropped by the reference (processing log): here it gets a
  * null key and a null value (every consumer drops it; a table upsert skips it) and is counted. */
 #define KHIP_FMT_NONE 0
@@ -815,6 +816,8 @@ khip_status khip_comm_destroy(khip_comm* c);
 #define KHIP_FMT_DELIMITED 2
 #define KHIP_FMT_JSON 3
 #define KHIP_FMT_AVRO 4
+#define KHIP_FMT_PROTOBUF 5       /* Confluent framing (schema registry) + one proto3 message */
+#define KHIP_FMT_PROTOBUF_NOSR 6  /* the bare message, no registry                             */
 /* Avro writer-schema field types (primitive; unions of null and one of them via avro_field_union) */
 #define KHIP_AVRO_BOOLEAN 1
 #define KHIP_AVRO_INT 2
@@ -823,13 +826,71 @@ khip_status khip_comm_destroy(khip_comm* c);
 #define KHIP_AVRO_DOUBLE 5
 #define KHIP_AVRO_STRING 6
 #define KHIP_AVRO_BYTES 7
+/* PROTOBUF values (deserialization; value_format = KHIP_FMT_PROTOBUF / KHIP_FMT_PROTOBUF_NOSR; a
+ * protobuf key format is KHIP_E_UNSUPPORTED).  protobuf/ProtobufSerdeFactory.java:168-260 (Confluent's
+ * ProtobufConverter) and protobuf/ProtobufNoSRConverter.java:56-157 (DynamicMessage.parseFrom against
+ * the schema of the ksql columns) both read through ConnectDataTranslator, so the name matching and
+ * the accepted types are AVRO's above.
+ *   framing  PROTOBUF: byte 0x00, the schema id as 4 bytes big-endian, the message-index list (a
+ *            zig-zag varint count, then that many zig-zag varint indexes; [0] is the one byte 0x00),
+ *            then the message.  Only the first message of the schema is read here: the list 00 and
+ *            its long form 02 00 are accepted, any other list is a deserialization error (such a
+ *            source stays with the reference).  PROTOBUF_NOSR: no framing; a
+ *            zero-length value is a message with every field absent.
+ *   writer   avro_field_types[w] = KHIP_PROTO_<type>; avro_field_union[w] = presence |
+ *            KHIP_PROTO_FIELD(number), presence 0 (none: an absent field reads as 0 / 0.0 / "") or 1
+ *            (explicit, proto3 `optional`: absent reads as NULL); avro_field_names[w] its name.  For
+ *            NOSR the Java side passes the ksql columns in order with numbers 1..n.
+ *            Connect types: int32 / sint32 / sfixed32 → INT32; every other integer → INT64 (uint32 /
+ *            fixed32 as their unsigned value, uint64 / fixed64 as the same 64 bits); float widened as
+ *            (double) f; bool; string and enum → STRING; bytes → BYTES.
+ *   parsing  protobuf-java's DynamicMessage: fields in any order, the last occurrence of a scalar
+ *            wins, an unknown number is skipped by its wire type (0, 1, 2, 5), a known field with
+ *            the wrong wire type is skipped as unknown (it reads as absent); int32 keeps the low 32
+ *            bits of its varint; sint32 / sint64 are zig-zag; bool is varint != 0; a string's bytes
+ *            must be valid UTF-8.
+ *   errors   (null key, null value, counted): a truncated varint or one longer than 10 bytes, a
+ *            length or fixed field past the end, field number 0, wire types 3, 4, 6, 7, a wrong
+ *            magic byte, another schema id than avro_schema_id (when >= 0), fewer than 6 framing
+ *            bytes.  Known divergence: protobuf-java skips an unknown proto2 group (wire type 3);
+ *            here the record fails.
+ * KHIP_E_INVALID at create: a field number outside 1..2^29 - 1, a duplicate number, an unknown type.
+ * Not on this path (KHIP_E_UNSUPPORTED at create: KHIP_PROTO_MESSAGE / KHIP_PROTO_REPEATED writer
+ * fields, a protobuf key format): wrapper messages (nullableRepresentation = wrapper), nested
+ * messages, maps, repeated source fields, unwrapPrimitives, protobuf keys. */
+#define KHIP_PROTO_INT32 1
+#define KHIP_PROTO_SINT32 2
+#define KHIP_PROTO_SFIXED32 3
+#define KHIP_PROTO_UINT32 4
+#define KHIP_PROTO_FIXED32 5
+#define KHIP_PROTO_INT64 6
+#define KHIP_PROTO_SINT64 7
+#define KHIP_PROTO_SFIXED64 8
+#define KHIP_PROTO_UINT64 9
+#define KHIP_PROTO_FIXED64 10
+#define KHIP_PROTO_FLOAT 11
+#define KHIP_PROTO_DOUBLE 12
+#define KHIP_PROTO_BOOL 13
+#define KHIP_PROTO_STRING 14
+#define KHIP_PROTO_BYTES 15
+#define KHIP_PROTO_ENUM 16
+/* what the Java side passes for a writer field this path does not read, so that the create fails
+ * with KHIP_E_UNSUPPORTED rather than the field being skipped: a nested message, map or wrapper
+ * (KHIP_PROTO_MESSAGE), a repeated field (KHIP_PROTO_REPEATED OR-ed into its element type) */
+#define KHIP_PROTO_MESSAGE 17
+#define KHIP_PROTO_REPEATED 0x20
+/* the field number (1..2^29 - 1), OR-ed into the avro_field_union entry above its presence bit.
+ * (Sixteen types and 2^29 numbers need 33 bits, so the number cannot share the type's 32-bit entry.) */
+#define KHIP_PROTO_FIELD(number) ((int32_t)(number) << 1)
+/* khip_sink_desc.value_format bit: the `optional` representation (see "PROTOBUF values (sink)") */
+#define KHIP_PROTO_OPTIONAL 0x100
 #define KHIP_TYPE_STRING 3  /* VARCHAR: keys → UTF-8 key columns; value fields are only checked for
                                NULL (an INT64 column of zeros + validity: what COUNT(col) reads)  */
 
 typedef struct khip_serde_desc {
   int32_t key_format;              /* KHIP_FMT_NONE or KHIP_FMT_KAFKA                          */
   int32_t key_type;                /* KHIP_TYPE_INT32 / INT64 (→ int64 keys) / STRING (→ UTF-8) */
-  int32_t value_format;            /* KHIP_FMT_KAFKA / DELIMITED / JSON / AVRO                 */
+  int32_t value_format;            /* KHIP_FMT_KAFKA / DELIMITED / JSON / AVRO / PROTOBUF[_NOSR] */
   int32_t n_fields;                /* value schema columns, in order                            */
   const int32_t* field_types;      /* KHIP_TYPE_INT32 / INT64 / DOUBLE / STRING                 */
   const char* const* field_names;  /* JSON / AVRO: column names as ksqlDB stores them           */
@@ -837,12 +898,15 @@ typedef struct khip_serde_desc {
   int32_t delimiter;               /* DELIMITED: the VALUE_DELIMITER byte (',')                 */
   int32_t device;
   /* AVRO: the writer schema (a record of avro_n_fields fields, in writer order) registered under
-   * avro_schema_id (-1: accept any id; a different id is a deserialization error) */
+   * avro_schema_id (-1: accept any id; a different id is a deserialization error).
+   * PROTOBUF / PROTOBUF_NOSR: the same fields carry the writer message (the names stay, for the
+   * ABI): avro_field_types = KHIP_PROTO_*, avro_field_union = presence | KHIP_PROTO_FIELD(number),
+   * any order; avro_schema_id is ignored for NOSR */
   int32_t avro_schema_id;
   int32_t avro_n_fields;
   const char* const* avro_field_names;
-  const int32_t* avro_field_types;  /* KHIP_AVRO_*                                               */
-  const int32_t* avro_field_union;  /* 0: plain; 1: ["null", T]; 2: [T, "null"]                  */
+  const int32_t* avro_field_types;  /* KHIP_AVRO_* (protobuf: KHIP_PROTO_*)                        */
+  const int32_t* avro_field_union;  /* 0: plain; 1: ["null", T]; 2: [T, "null"] (protobuf: above)  */
 } khip_serde_desc;
 
 /* One batch of Kafka records as the consumer returns them (arrival order). */
@@ -887,7 +951,7 @@ khip_status khip_serde_destroy(khip_serde* s);
  *          158-161) → compact object in column order; DELIMITED: KsqlDelimitedSerializer
  *          (delimited/KsqlDelimitedSerializer.java:59-71; commons-csv 1.4 MINIMAL quoting, null =
  *          empty field); KAFKA: the single column's primitive bytes (a NULL column = a null value).
- *          AVRO: see "AVRO values" below.
+ *          AVRO: see "AVRO values" below.  PROTOBUF / PROTOBUF_NOSR: see "PROTOBUF values (sink)".
  *          A tombstone row (the row left the table / a HAVING delete) has a null value.
  * Numbers print as Long.toString / Double.toString (JDK 19+ shortest-decimal specification;
  * non-finite doubles as the JSON strings "NaN" / "Infinity" / "-Infinity", Jackson's default).
@@ -902,12 +966,13 @@ khip_status khip_serde_destroy(khip_serde* s);
  * BY_OFFSET), OR-ed into a khip_sink_desc.value_types entry like KHIP_AGG_K into a kind: no such
  * bits is a scalar column; KHIP_SINK_ARRAY(L), 1 <= L <= 32767, an ARRAY of the base type (INT32 /
  * INT64 / DOUBLE) with L slots per row, L being khip_agg_result_len() of the aggregate behind the
- * column (the sink has no 29-word limit of its own).  Only a JSON or an AVRO value carries one (the
+ * column (the sink has no 29-word limit of its own).  Only a JSON, AVRO or PROTOBUF value carries
+ * one (the
  * reference rejects such a statement for DELIMITED and KAFKA at plan time).  In JSON the column
  * prints, after its name, as the compact list [e0,e1,...], every element as a scalar of its type
  * prints (a NULL element as null, a non-finite DOUBLE as its string), the empty list as []; in
- * AVRO it is one block (see "AVRO values").  The column itself is never SQL NULL.  The row's
- * list: see khip_sink_rows.  KHIP_E_INVALID from khip_sink_create: an
+ * AVRO it is one block (see "AVRO values"), in PROTOBUF a packed repeated field.  The column itself
+ * is never SQL NULL.  The row's list: see khip_sink_rows.  KHIP_E_INVALID from khip_sink_create: an
  * ARRAY column with value format KAFKA or DELIMITED; the bits on a KHIP_SINK_SRC_WS / _WE column;
  * negative bits; two value columns reading one rows column with different L or base type when
  * either is an ARRAY.  Key columns are scalar: the bits on a key type are an unknown key type. */
@@ -919,7 +984,8 @@ typedef struct khip_sink_desc {
   const int32_t* key_types;        /* KHIP_TYPE_INT32 / INT64 / DOUBLE / STRING                   */
   const char* const* key_names;    /* JSON object field names (several key columns)              */
   int32_t window_kind;             /* KHIP_WINDOW_*: the table's window (NONE: plain key)        */
-  int32_t value_format;            /* KHIP_FMT_KAFKA / JSON / DELIMITED / AVRO                   */
+  int32_t value_format;            /* KHIP_FMT_KAFKA / JSON / DELIMITED / AVRO / PROTOBUF[_NOSR]
+                                      [| KHIP_PROTO_OPTIONAL]                                    */
   int32_t n_value_cols;            /* 0..KHIP_SINK_MAX_COLS (KAFKA: 1)                            */
   const int32_t* value_types;      /* KHIP_TYPE_INT32 / INT64 / DOUBLE [| KHIP_SINK_ARRAY(L)]     */
   const char* const* value_names;  /* JSON field names, in output column order (AVRO: ignored,
@@ -959,8 +1025,42 @@ khip_status khip_sink_create(const khip_sink_desc* desc, khip_sink** out);
  * encode uses the new id.  KHIP_E_INVALID: a null handle, a negative id, a handle whose value
  * format is not AVRO.  khip_sink_encode on an AVRO sink with no id set: KHIP_E_STATE.
  * Not on this path (they stay with the reference): AVRO keys, a VALUE_SCHEMA_ID physical schema
- * (plain or [T,"null"] fields), WRAP_SINGLE_VALUE=false, STRING / DECIMAL columns, PROTOBUF. */
+ * (plain or [T,"null"] fields), WRAP_SINGLE_VALUE=false, STRING / DECIMAL columns. */
 khip_status khip_sink_set_avro_schema_id(khip_sink* s, int32_t schema_id);
+
+/* PROTOBUF values (sink; value_format = KHIP_FMT_PROTOBUF or KHIP_FMT_PROTOBUF_NOSR, optionally
+ * | KHIP_PROTO_OPTIONAL; keys stay KAFKA / JSON / DELIMITED, a protobuf key is KHIP_E_UNSUPPORTED).
+ * The bytes of protobuf/ProtobufSerdeFactory.java:168-260 (Confluent's ProtobufConverter and
+ * KafkaProtobufSerializer) and protobuf/ProtobufNoSRConverter.java:56-157 (Message.writeTo) for the
+ * one message ksqlDB generates: value column i (from 0, output order) is field number i + 1, INT32
+ * = int32, INT64 = int64, DOUBLE = double, an ARRAY column a repeated field of its element type;
+ * KHIP_SINK_SRC_WS / _WE columns are int64 fields like any other.
+ *   framing  PROTOBUF: byte 0x00, the schema id as 4 bytes big-endian, the message-index list [0]
+ *            as the one byte 0x00.  PROTOBUF_NOSR: none.
+ *   field    in field-number order: the tag, the varint of number << 3 | wire type (two bytes from
+ *            field 16 on), then the value;
+ *   INT32 / INT64  wire type 0: the value sign-extended to 64 bits as a base-128 varint (a negative
+ *            int32 takes 10 bytes);
+ *   DOUBLE   wire type 1: the 8 raw IEEE bytes little-endian (NaN payloads, -0.0, denormals survive);
+ *   ARRAY    packed: one tag of wire type 2, the varint byte length of the payload, the elements
+ *            back to back; the empty list writes nothing.  The column is never NULL.
+ *   default representation (no bit): a scalar is written only when it is non-NULL and its raw bits
+ *            are not zero — 0 and +0.0 are absent, -0.0 and every NaN are written (proto3 has no
+ *            NULL: a NULL reads back as the default);
+ *   KHIP_PROTO_OPTIONAL (nullableRepresentation = optional): a scalar is written whenever it is
+ *            non-NULL, zero included; arrays as above (proto3 has no optional repeated field).
+ *            The bit on any other value format is KHIP_E_INVALID.
+ * A tombstone row has a null value; a row whose fields are all absent has a non-null value holding
+ * the framing alone (NOSR: zero bytes).  value_names is ignored.
+ * A NULL array element (null byte 2, the KHIP_AGG_KEEP_NULLS N forms) has no protobuf form:
+ * khip_sink_encode answers KHIP_E_UNSUPPORTED and writes nothing when any row's list holds one (the
+ * measure pass finds it); the Java side keeps such a query on the CPU at plan time.
+ * khip_sink_set_schema_id sets the id of the AVRO or the PROTOBUF framing, and may be called again
+ * between encodes.  KHIP_E_INVALID: a null handle, a negative id, a handle of any other value format
+ * (PROTOBUF_NOSR included).  khip_sink_encode on a PROTOBUF sink with no id set: KHIP_E_STATE.
+ * Not on this path (they stay with the reference): protobuf keys, nullableRepresentation = wrapper,
+ * nested messages, STRING / DECIMAL columns. */
+khip_status khip_sink_set_schema_id(khip_sink* s, int32_t schema_id);
 
 /* One GROUP BY column of a batch (same memory kind as the batch). */
 typedef struct khip_key_col {

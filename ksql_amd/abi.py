@@ -189,7 +189,7 @@ class SinkOut(C.Structure):
                 ("value_bytes", C.c_void_p), ("value_null", C.c_void_p), ("key_len", i64), ("value_len", i64)]
 
 
-FMT = {"NONE": 0, "KAFKA": 1, "DELIMITED": 2, "JSON": 3, "AVRO": 4}
+FMT = {"NONE": 0, "KAFKA": 1, "DELIMITED": 2, "JSON": 3, "AVRO": 4, "PROTOBUF": 5, "PROTOBUF_NOSR": 6}
 SINK_SRC = {"WS": -2, "WE": -3}
 
 
@@ -203,6 +203,22 @@ def SINK_ARRAY(L):
 SINK_ARRAY_STAGE = 32768
 
 AVRO_TYPE = {"boolean": 1, "int": 2, "long": 3, "float": 4, "double": 5, "string": 6, "bytes": 7}
+# KHIP_PROTO_*: the sixteen scalar types of a protobuf writer field
+PROTO_TYPE = {"int32": 1, "sint32": 2, "sfixed32": 3, "uint32": 4, "fixed32": 5, "int64": 6, "sint64": 7,
+              "sfixed64": 8, "uint64": 9, "fixed64": 10, "float": 11, "double": 12, "bool": 13, "string": 14,
+              "bytes": 15, "enum": 16}
+PROTO_MESSAGE = 17      # KHIP_PROTO_MESSAGE: a nested message, map or wrapper (refused at create)
+PROTO_REPEATED = 0x20   # KHIP_PROTO_REPEATED, OR-ed into the element type (refused at create)
+PROTO_OPTIONAL = 0x100  # KHIP_PROTO_OPTIONAL, OR-ed into a sink's protobuf value format
+PROTO_FORMATS = ("PROTOBUF", "PROTOBUF_NOSR")
+
+
+def PROTO_FIELD(number):
+    """KHIP_PROTO_FIELD(number): the field number, OR-ed into the avro_field_union entry above the
+    presence bit."""
+    return int(number) << 1
+
+
 TYPE_STRING = 3
 COMM_ID_BYTES = 128
 
@@ -258,6 +274,7 @@ PRODUCT_ONLY = {
     "sink_key": ([_P, C.POINTER(Batch), C.POINTER(KeyCol), C.POINTER(Batch)]),
     "sink_encode": ([_P, C.POINTER(SinkRows), C.POINTER(SinkOut)]),
     "sink_set_avro_schema_id": ([_P, i32]),
+    "sink_set_schema_id": ([_P, i32]),
     "sink_sync": ([_P]),
     "sink_destroy": ([_P]),
 }
@@ -1003,14 +1020,17 @@ class Comm:
 
 
 class SerdeHandle:
-    """khip_serde_*: Kafka record bytes (KAFKA / DELIMITED / JSON / AVRO) → a device batch."""
+    """khip_serde_*: Kafka record bytes (KAFKA / DELIMITED / JSON / AVRO / PROTOBUF[_NOSR]) → a device batch."""
 
     def __init__(self, lib, value_format, fields, key_type="INT64", key_format="KAFKA", delimiter=",",
-                 device=0, avro_schema=None, avro_schema_id=-1):
+                 device=0, avro_schema=None, avro_schema_id=-1, proto_schema=None):
         """fields: [(name, type, out_col or -1)], type in INT32 / INT64 / DOUBLE / STRING.
         avro_schema (AVRO): the writer record's fields [(name, avro type, union)], avro type in
         boolean / int / long / float / double / string / bytes, union 0 (plain), 1 (["null", T]) or
-        2 ([T, "null"]); registered under avro_schema_id (-1: any id)."""
+        2 ([T, "null"]); registered under avro_schema_id (-1: any id).
+        proto_schema (PROTOBUF / PROTOBUF_NOSR): the writer message's fields [(name, proto type,
+        number, presence)], proto type a PROTO_TYPE name (or the ABI's integer), presence 0 or 1;
+        avro_schema_id is the expected schema id of the PROTOBUF framing."""
         self.lib = lib
         tmap = dict(TYPE, STRING=TYPE_STRING)
         self._ft = (i32 * len(fields))(*[tmap[t] for _, t, _ in fields])
@@ -1018,8 +1038,13 @@ class SerdeHandle:
         self._fo = (i32 * len(fields))(*[o for _, _, o in fields])
         self.n_out = max([o for _, _, o in fields] + [-1]) + 1
         aw = avro_schema or []
+        if proto_schema is not None:  # the same descriptor fields carry the protobuf writer message
+            aw = [(n, t if isinstance(t, int) else PROTO_TYPE[t], (p & 1) | PROTO_FIELD(num))
+                  for n, t, num, p in proto_schema]
+        else:
+            aw = [(n, AVRO_TYPE[t], u) for n, t, u in aw]
         self._an = (C.c_char_p * max(len(aw), 1))(*[n.encode() for n, _, _ in aw])
-        self._at = (i32 * max(len(aw), 1))(*[AVRO_TYPE[t] for _, t, _ in aw])
+        self._at = (i32 * max(len(aw), 1))(*[t for _, t, _ in aw])
         self._au = (i32 * max(len(aw), 1))(*[u for _, _, u in aw])
         self.desc = SerdeDesc(FMT[key_format], tmap[key_type], FMT[value_format], len(fields), self._ft, self._fn,
                               self._fo, ord(delimiter), device, avro_schema_id, len(aw), self._an, self._at,
@@ -1116,11 +1141,13 @@ class SinkHandle:
     columns → the serialized composite key."""
 
     def __init__(self, lib, key_format, key_cols, value_format, value_cols, window_kind="NONE", delimiter=",",
-                 device=0, avro_schema_id=None):
+                 device=0, avro_schema_id=None, schema_id=None, proto_optional=False):
         """key_cols: [(name, type)]; value_cols: [(name, type, src)] with src a rows column index or
         "WS" / "WE"; types INT32 / INT64 / DOUBLE / STRING (keys).  (name, type, src, L) is an ARRAY
         column of L slots per row (KHIP_SINK_ARRAY(L); JSON or AVRO values), type its element type.
-        avro_schema_id: the AVRO value format's schema id (set_avro_schema_id)."""
+        avro_schema_id: the AVRO value format's schema id (set_avro_schema_id).  schema_id: the AVRO
+        or PROTOBUF framing's id (set_schema_id).  proto_optional: KHIP_PROTO_OPTIONAL, the `optional`
+        representation of a PROTOBUF / PROTOBUF_NOSR value.  value_format may also be the ABI's integer."""
         self.lib = lib
         tmap = dict(TYPE, STRING=TYPE_STRING)
         nk, nv = len(key_cols), len(value_cols)
@@ -1135,12 +1162,21 @@ class SinkHandle:
         self._vn = (C.c_char_p * max(nv, 1))(*[c[0].encode() for c in value_cols])
         self._vs = (i32 * max(nv, 1))(*[SINK_SRC[c[2]] if isinstance(c[2], str) else c[2] for c in value_cols])
         self.key_cols, self.value_cols = key_cols, value_cols
-        self.desc = SinkDesc(FMT[key_format], nk, self._kt, self._kn, WINDOW[window_kind], FMT[value_format], nv,
+        vf = value_format if isinstance(value_format, int) else FMT[value_format]
+        kf = key_format if isinstance(key_format, int) else FMT[key_format]
+        self.desc = SinkDesc(kf, nk, self._kt, self._kn, WINDOW[window_kind],
+                             vf | (PROTO_OPTIONAL if proto_optional else 0), nv,
                              self._vt, self._vn, self._vs, ord(delimiter), device)
         self.h = C.c_void_p()
         lib.check(lib.sink_create(C.byref(self.desc), C.byref(self.h)), "sink_create")
         if avro_schema_id is not None:
             self.set_avro_schema_id(avro_schema_id)
+        if schema_id is not None:
+            self.set_schema_id(schema_id)
+
+    def set_schema_id(self, schema_id):
+        """khip_sink_set_schema_id: the id in the framing of the AVRO / PROTOBUF values encoded from now on."""
+        self.lib.check(self.lib.sink_set_schema_id(self.h, int(schema_id)), "sink_set_schema_id")
 
     def set_avro_schema_id(self, schema_id):
         """khip_sink_set_avro_schema_id: the id in the header of the AVRO values encoded from now on."""

@@ -1,7 +1,7 @@
 // khip_serde.hip — deserialization of Kafka record bytes into device columns (gfx950).
 //
 // Replaces, for the hot path's source topics, the per-record GenericKeySerDe / GenericRowSerDe
-// deserializers (KAFKA, DELIMITED, JSON, AVRO; include/ksqldb_hip.h "deserialization") that box every
+// deserializers (KAFKA, DELIMITED, JSON, AVRO, PROTOBUF; include/ksqldb_hip.h "deserialization") that box every
 // record into a GenericKey / GenericRow before the aggregate or join sees it — the reference's
 // documented bottleneck (ksqldb-benchmark/README.md:7-9).
 //
@@ -817,6 +817,213 @@ __global__ __launch_bounds__(64) void k_serde_fix(const int64_t* __restrict__ fi
   else ((double*)o.col[c])[row] = d;
 }
 
+// ------------------------------------------------------------------ PROTOBUF values
+//
+// PROTOBUF / PROTOBUF_NOSR (include/ksqldb_hip.h, "PROTOBUF values (deserialization)") have a kernel
+// and a parameter block of their own, so that k_serde_decode and SerdeParams stay as they are for
+// the other formats (profiles/protobuf/README.md).  The writer message's fields sit in a table
+// sorted by field number (numbers are sparse and reach 2^29 - 1): numbers up to 32 index it
+// directly, the others by binary search.
+
+constexpr int PB_DIRECT = 32;
+constexpr uint32_t PB_MAX_FIELD = (1u << 29) - 1;
+
+struct ProtoParams {
+  int32_t key_format, key_type, framed, id, n_out, n_ent, incompat;
+  uint32_t num[SD_MAX_FIELDS];   // field numbers, ascending
+  // per entry: KHIP_PROTO_* type (bits 0-4), explicit presence (bit 5), the column's KHIP_TYPE_*
+  // (bits 6-7), output column + 1 (bits 8-13; 0: not read, or a later writer field owns the column)
+  uint32_t meta[SD_MAX_FIELDS];
+  int8_t direct[PB_DIRECT + 1];  // field number 1..32 → entry, or -1
+};
+
+// the wire type a field of this type arrives with
+__host__ __device__ inline int pb_wire(int pt) {
+  switch (pt) {
+    case KHIP_PROTO_SFIXED32: case KHIP_PROTO_FIXED32: case KHIP_PROTO_FLOAT: return 5;
+    case KHIP_PROTO_SFIXED64: case KHIP_PROTO_FIXED64: case KHIP_PROTO_DOUBLE: return 1;
+    case KHIP_PROTO_STRING: case KHIP_PROTO_BYTES: return 2;
+    default: return 0;
+  }
+}
+
+// s[0..n) is well-formed UTF-8 (the proto3 rule for a string field)
+__device__ __forceinline__ bool pb_utf8_ok(const uint8_t* s, int n) {
+  for (int i = 0; i < n;) {
+    if (s[i] < 0x80) {
+      i++;
+      continue;
+    }
+    uint32_t cp;
+    const int l = utf8_dec(s, n, i, &cp);
+    if (!l) return false;
+    i += l;
+  }
+  return true;
+}
+
+__global__ __launch_bounds__(256) void k_serde_decode_proto(ProtoParams q, int64_t n, const int64_t* __restrict__ koff,
+                                                            const uint8_t* __restrict__ kbytes,
+                                                            const uint8_t* __restrict__ kval,
+                                                            const int64_t* __restrict__ voff,
+                                                            const uint8_t* __restrict__ vbytes,
+                                                            const uint8_t* __restrict__ vval, SerdeOut o) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ uint32_t vst[4][SERDE_VWORDS];
+  __shared__ uint32_t kst[4][SERDE_KWORDS];
+  const int64_t w0 = i - lane, wl = (n - 1 < w0 + 63) ? n - 1 : w0 + 63;
+  int64_t vshift = 0, kshift = 0;
+  bool vstaged = false, kstaged = false;
+  if (w0 < n) {
+    vstaged = stage_bytes<SERDE_VWORDS>(vst[wave], vbytes, voff[w0], voff[wl + 1], lane, &vshift);
+    if (q.key_format != KHIP_FMT_NONE && kbytes)
+      kstaged = stage_bytes<SERDE_KWORDS>(kst[wave], kbytes, koff[w0], koff[wl + 1], lane, &kshift);
+  }
+  __syncthreads();
+  auto vat = [&](int64_t x) { return vstaged ? (const uint8_t*)vst[wave] + (x - vshift) : vbytes + x; };
+  auto kat = [&](int64_t x) { return kstaged ? (const uint8_t*)kst[wave] + (x - kshift) : kbytes + x; };
+  bool ok = i < n;
+  bool key_ok = false, row_ok = false;
+  uint32_t fnull = 0;
+  if (i < n) {
+    if (q.key_format == KHIP_FMT_NONE) {
+      key_ok = true;
+      if (o.key_i64) o.key_i64[i] = 0;
+    } else if (bit_get(kval, i)) {
+      const int64_t k0 = koff[i], kn = koff[i + 1] - k0;
+      if (q.key_type == KHIP_TYPE_INT64) {
+        if (kn == 8) o.key_i64[i] = (int64_t)be_load(kat(k0), 8);
+        else ok = false;
+      } else if (q.key_type == KHIP_TYPE_INT32) {
+        if (kn == 4) o.key_i64[i] = (int64_t)(int32_t)(uint32_t)be_load(kat(k0), 4);
+        else ok = false;
+      }
+      key_ok = true;
+    }
+    row_ok = bit_get(vval, i);
+    if (ok && row_ok) {
+      const int64_t v0 = voff[i], vn = voff[i + 1] - v0;
+      const uint8_t* p = vat(v0);
+      for (int c = 0; c < q.n_out; c++) fnull |= 1u << c;
+      if (q.incompat) ok = false;
+      int64_t j = 0;
+      if (ok && q.framed) {
+        // magic 0, the schema id, the message-index list: [0] as 00 or as 02 00 (count 1, index 0)
+        if (vn < 6 || p[0] != 0) ok = false;
+        else if (q.id >= 0 && (int32_t)(uint32_t)be_load(p + 1, 4) != q.id) ok = false;
+        j = 5;
+        uint64_t cnt = 0, idx = 0;
+        if (ok && !avro_varint(p, vn, &j, 10, &cnt)) ok = false;
+        if (ok && cnt != 0) {
+          if (cnt != 2 || !avro_varint(p, vn, &j, 10, &idx) || idx != 0) ok = false;
+        }
+      }
+      uint32_t seen = 0;  // per table entry: the field occurred
+      while (ok && j < vn) {
+        uint64_t tag;
+        if (!avro_varint(p, vn, &j, 10, &tag)) { ok = false; break; }
+        const uint32_t num = (uint32_t)tag >> 3;
+        const int wt = (int)(tag & 7);
+        if (num == 0 || wt == 3 || wt == 4 || wt > 5) { ok = false; break; }
+        uint64_t raw = 0;
+        int64_t s0 = 0;
+        int32_t sl = 0;
+        if (wt == 0) {
+          if (!avro_varint(p, vn, &j, 10, &raw)) { ok = false; break; }
+        } else if (wt == 1) {
+          if (vn - j < 8) { ok = false; break; }
+          raw = le_load(p + j, 8);
+          j += 8;
+        } else if (wt == 5) {
+          if (vn - j < 4) { ok = false; break; }
+          raw = le_load(p + j, 4);
+          j += 4;
+        } else {
+          uint64_t l;
+          if (!avro_varint(p, vn, &j, 10, &l)) { ok = false; break; }
+          sl = (int32_t)(uint32_t)l;
+          if (sl < 0 || sl > vn - j) { ok = false; break; }
+          s0 = j;
+          j += sl;
+        }
+        int e = -1;
+        if (num <= PB_DIRECT) {
+          e = q.direct[num];
+        } else {
+          int lo = 0, hi = q.n_ent;
+          while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (q.num[mid] < num) lo = mid + 1;
+            else hi = mid;
+          }
+          if (lo < q.n_ent && q.num[lo] == num) e = lo;
+        }
+        if (e < 0) continue;  // an unknown field
+        const uint32_t m = q.meta[e];
+        const int pt = (int)(m & 31);
+        if (wt != pb_wire(pt)) continue;  // a known field with another wire type: skipped as unknown
+        if (pt == KHIP_PROTO_STRING && !pb_utf8_ok(p + s0, sl)) { ok = false; break; }
+        seen |= 1u << e;
+        const int c = (int)((m >> 8) & 63) - 1;
+        if (c < 0) continue;
+        uint64_t bits;
+        switch (pt) {
+          case KHIP_PROTO_INT32: bits = (uint64_t)(int64_t)(int32_t)(uint32_t)raw; break;
+          case KHIP_PROTO_SINT32: bits = (uint64_t)(int64_t)zz32((uint32_t)raw); break;
+          case KHIP_PROTO_SFIXED32: bits = (uint64_t)(int64_t)(int32_t)(uint32_t)raw; break;
+          case KHIP_PROTO_UINT32: bits = (uint64_t)(uint32_t)raw; break;
+          case KHIP_PROTO_SINT64: bits = (uint64_t)zz64(raw); break;
+          case KHIP_PROTO_FLOAT: {
+            const uint32_t u = (uint32_t)raw;
+            float fv;
+            __builtin_memcpy(&fv, &u, 4);
+            const double dv = (double)fv;
+            __builtin_memcpy(&bits, &dv, 8);
+            break;
+          }
+          case KHIP_PROTO_BOOL: bits = raw != 0; break;
+          default: bits = raw; break;  // fixed32 (zero-extended), the 64-bit integers, double
+        }
+        fnull &= ~(1u << c);
+        const int kt = (int)((m >> 6) & 3);
+        if (kt == KHIP_TYPE_INT32) ((int32_t*)o.col[c])[i] = (int32_t)bits;
+        else if (kt == KHIP_TYPE_STRING) ((int64_t*)o.col[c])[i] = 0;
+        else ((uint64_t*)o.col[c])[i] = bits;
+      }
+      // the fields that never occurred: the default without presence, NULL with it
+      for (int e = 0; ok && e < q.n_ent; e++) {
+        if ((seen >> e) & 1) continue;
+        const uint32_t m = q.meta[e];
+        const int c = (int)((m >> 8) & 63) - 1;
+        if (c < 0 || ((m >> 5) & 1)) continue;
+        fnull &= ~(1u << c);
+        if ((int)((m >> 6) & 3) == KHIP_TYPE_INT32) ((int32_t*)o.col[c])[i] = 0;
+        else ((int64_t*)o.col[c])[i] = 0;
+      }
+    }
+  }
+  const bool err = i < n && !ok;
+  const uint64_t bk = __ballot(i < n && ok && key_ok), br = __ballot(i < n && ok && row_ok);
+  const int64_t wbase = i - lane;
+  if (lane == 0 && wbase < n) {
+    const int64_t nbytes = std::min<int64_t>(8, (n - wbase + 7) / 8);
+    for (int b = 0; b < nbytes; b++) {
+      o.key_valid[wbase / 8 + b] = (uint8_t)(bk >> (8 * b));
+      o.row_valid[wbase / 8 + b] = (uint8_t)(br >> (8 * b));
+    }
+  }
+  for (int c = 0; c < q.n_out; c++) {
+    const uint64_t bv = __ballot(i < n && ok && row_ok && !((fnull >> c) & 1));
+    if (lane == 0 && wbase < n) {
+      const int64_t nbytes = std::min<int64_t>(8, (n - wbase + 7) / 8);
+      for (int b = 0; b < nbytes; b++) o.col_valid[c][wbase / 8 + b] = (uint8_t)(bv >> (8 * b));
+    }
+  }
+  const uint64_t be = __ballot(err);
+  if (lane == 0 && be) atomicAdd(o.n_err, (unsigned long long)__popcll(be));
+}
+
 }  // namespace khip
 
 using namespace khip;
@@ -824,6 +1031,8 @@ using namespace khip;
 struct khip_serde {
   khip_serde_desc desc{};
   SerdeParams q{};
+  ProtoParams pq{};  // PROTOBUF / PROTOBUF_NOSR: the decode kernel's parameters
+  bool proto = false;
   std::vector<int32_t> out_type;  // per output column: element type
   int device = 0;
   hipStream_t stream = nullptr;
@@ -851,8 +1060,13 @@ khip_status khip_serde_create(const khip_serde_desc* d, khip_serde** out) {
       d->key_type != KHIP_TYPE_STRING)
     return fail(KHIP_E_UNSUPPORTED, "key type");
   if (d->value_format != KHIP_FMT_KAFKA && d->value_format != KHIP_FMT_DELIMITED && d->value_format != KHIP_FMT_JSON &&
-      d->value_format != KHIP_FMT_AVRO)
-    return fail(KHIP_E_UNSUPPORTED, "value format (KAFKA, DELIMITED, JSON, AVRO)");
+      d->value_format != KHIP_FMT_AVRO && d->value_format != KHIP_FMT_PROTOBUF &&
+      d->value_format != KHIP_FMT_PROTOBUF_NOSR)
+    return fail(KHIP_E_UNSUPPORTED, "value format (KAFKA, DELIMITED, JSON, AVRO, PROTOBUF, PROTOBUF_NOSR)");
+  const bool proto = d->value_format == KHIP_FMT_PROTOBUF || d->value_format == KHIP_FMT_PROTOBUF_NOSR;
+  if (proto && (d->avro_n_fields < 0 || d->avro_n_fields > SD_MAX_FIELDS ||
+                (d->avro_n_fields && (!d->avro_field_names || !d->avro_field_types || !d->avro_field_union))))
+    return fail(KHIP_E_INVALID, "PROTOBUF writer message: 0..32 fields with names, types and numbers");
   if (d->value_format == KHIP_FMT_AVRO &&
       (d->avro_n_fields < 0 || d->avro_n_fields > SD_MAX_FIELDS || (d->avro_n_fields && (!d->avro_field_names ||
                                                                                      !d->avro_field_types))))
@@ -878,12 +1092,12 @@ khip_status khip_serde_create(const khip_serde_desc* d, khip_serde** out) {
     q.ftype[f] = t;
     q.fout[f] = d->field_out ? d->field_out[f] : f;
     if (q.fout[f] >= 0) n_out = std::max(n_out, q.fout[f] + 1);
-    if (d->value_format == KHIP_FMT_JSON || d->value_format == KHIP_FMT_AVRO) {
+    if (d->value_format == KHIP_FMT_JSON || d->value_format == KHIP_FMT_AVRO || proto) {
       const char* nm = d->field_names ? d->field_names[f] : nullptr;
       const size_t L = nm ? strlen(nm) : 0;
       if (!nm || L > SD_NAME_BYTES) {
         delete s;
-        return fail(KHIP_E_INVALID, "JSON / AVRO field names (<= 64 bytes) required");
+        return fail(KHIP_E_INVALID, "JSON / AVRO / PROTOBUF field names (<= 64 bytes) required");
       }
       q.name_len[f] = (int32_t)L;
       memcpy(q.name[f], nm, L);
@@ -924,7 +1138,74 @@ khip_status khip_serde_create(const khip_serde_desc* d, khip_serde** out) {
       if (!okt) q.avro_incompat = 1;
     }
   }
+  if (proto) {
+    // writer field → ksql field as for AVRO (ConnectDataTranslator.toKsqlStruct); the translator sets
+    // the columns in writer order, so of several writer fields landing in one column the last owns it
+    ProtoParams& pq = s->pq;
+    s->proto = true;
+    pq.key_format = d->key_format;
+    pq.key_type = d->key_type;
+    pq.framed = d->value_format == KHIP_FMT_PROTOBUF;
+    pq.id = pq.framed ? d->avro_schema_id : -1;
+    pq.n_ent = d->avro_n_fields;
+    struct Ent { uint32_t num; int pt, pres, f; };
+    std::vector<Ent> ents;
+    for (int w = 0; w < d->avro_n_fields; w++) {
+      const int pt = d->avro_field_types[w], un = d->avro_field_union[w];
+      const char* wn = d->avro_field_names[w];
+      if (pt == KHIP_PROTO_MESSAGE || (pt > 0 && (pt & KHIP_PROTO_REPEATED) && (pt & ~KHIP_PROTO_REPEATED) <= KHIP_PROTO_MESSAGE)) {
+        delete s;
+        return fail(KHIP_E_UNSUPPORTED, "PROTOBUF writer field: nested, map, wrapper and repeated fields stay with the reference");
+      }
+      if (pt < KHIP_PROTO_INT32 || pt > KHIP_PROTO_ENUM || !wn) {
+        delete s;
+        return fail(KHIP_E_INVALID, "PROTOBUF writer field: unknown type or no name");
+      }
+      const uint32_t num = un < 0 ? 0 : (uint32_t)un >> 1;
+      if (num < 1 || num > PB_MAX_FIELD) {
+        delete s;
+        return fail(KHIP_E_INVALID, "PROTOBUF writer field number outside 1..2^29 - 1");
+      }
+      for (const Ent& e : ents)
+        if (e.num == num) {
+          delete s;
+          return fail(KHIP_E_INVALID, "PROTOBUF writer field number " + std::to_string(num) + " twice");
+        }
+      const std::string up = upper_utf8_host(wn);
+      int fx = -1, fu = -1;
+      for (int f = 0; f < d->n_fields; f++) {
+        const std::string kn(d->field_names[f]);
+        if (kn == wn && fx < 0) fx = f;
+        if (kn == up && fu < 0) fu = f;
+      }
+      const int f = fx >= 0 ? fx : fu;
+      if (f >= 0) {
+        for (Ent& e : ents)
+          if (e.f == f) e.f = -2;  // mapped (its type still counts), but a later field owns the column
+        const int kt = d->field_types[f];
+        const bool i32 = pt == KHIP_PROTO_INT32 || pt == KHIP_PROTO_SINT32 || pt == KHIP_PROTO_SFIXED32;
+        const bool i64 = pt >= KHIP_PROTO_UINT32 && pt <= KHIP_PROTO_FIXED64;
+        const bool flt = pt == KHIP_PROTO_FLOAT || pt == KHIP_PROTO_DOUBLE;
+        const bool okt = kt == KHIP_TYPE_STRING ? pt != KHIP_PROTO_BYTES
+                         : kt == KHIP_TYPE_INT64 ? (i32 || i64)
+                         : kt == KHIP_TYPE_INT32 ? i32
+                                                 : flt;
+        if (!okt) pq.incompat = 1;
+      }
+      ents.push_back(Ent{num, pt, un & 1, f});
+    }
+    std::sort(ents.begin(), ents.end(), [](const Ent& a, const Ent& b) { return a.num < b.num; });
+    for (int k = 0; k <= PB_DIRECT; k++) pq.direct[k] = -1;
+    for (size_t e = 0; e < ents.size(); e++) {
+      const int c = ents[e].f >= 0 ? q.fout[ents[e].f] : -1;
+      const int kt = ents[e].f >= 0 ? q.ftype[ents[e].f] : 0;
+      pq.num[e] = ents[e].num;
+      pq.meta[e] = (uint32_t)ents[e].pt | (uint32_t)ents[e].pres << 5 | (uint32_t)kt << 6 | (uint32_t)(c + 1) << 8;
+      if (ents[e].num <= (uint32_t)PB_DIRECT) pq.direct[ents[e].num] = (int8_t)e;
+    }
+  }
   q.n_out = n_out;
+  s->pq.n_out = n_out;
   s->out_type.assign(n_out, KHIP_TYPE_INT64);
   for (int f = 0; f < d->n_fields; f++)
     if (q.fout[f] >= 0) s->out_type[q.fout[f]] = q.ftype[f] == KHIP_TYPE_STRING ? KHIP_TYPE_INT64 : q.ftype[f];
@@ -999,7 +1280,10 @@ khip_status khip_serde_decode(khip_serde* s, const khip_raw_batch* in, khip_batc
   unsigned long long c2[2] = {0, 0};
   if (n > 0) {
     for (int attempt = 0; attempt < 2; attempt++) {
-      if (q.n_fields <= 4)
+      if (s->proto)
+        hipLaunchKernelGGL(k_serde_decode_proto, dim3(ceil_div(n, 256)), dim3(256), 0, s->stream, s->pq, n, koff, kb, kv,
+                           voff, vb, vv, o);
+      else if (q.n_fields <= 4)
         hipLaunchKernelGGL(k_serde_decode<4>, dim3(ceil_div(n, 256)), dim3(256), 0, s->stream, q, n, koff, kb, kv, voff, vb,
                            vv, o);
       else

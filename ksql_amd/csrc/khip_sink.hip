@@ -13,7 +13,8 @@
 // window suffix leave as 8-byte words), and a JSON column's '{' / ',' + escaped name + ':' is built
 // once on the host.  A sink with an ARRAY value column (KHIP_SINK_ARRAY: JSON lists) runs its own
 // instantiations, k_sink_measure<true> and k_sink_write_arr; a scalar sink's kernels carry none
-// of it.  A sink with AVRO values (the Confluent wire format of ksqlDB's own schema: scalars and
+// of it.  PROTOBUF values likewise run three kernels of their own ("the PROTOBUF sink's kernels").
+// A sink with AVRO values (the Confluent wire format of ksqlDB's own schema: scalars and
 // ARRAY columns, keys as above) runs three kernels of its own, "the AVRO sink's kernels" below: the
 // lengths in closed form, the same two stages on the way out.  Doubles print
 // through the Schubfach shortest-decimal algorithm (R. Giulietti 2020; java.lang.Double.toString
@@ -1120,6 +1121,242 @@ __global__ KHIP_SINK_WRITE_LB void k_sink_write_arr_avro(const SinkParams* __res
   }
 }
 
+// ------------------------------------------------------------------ the PROTOBUF sink's kernels
+//
+// PROTOBUF / PROTOBUF_NOSR values (include/ksqldb_hip.h, "PROTOBUF values (sink)") run three kernels
+// of their own with the AVRO kernels' structure, so that every other format's kernels stay as they
+// are.  schema_id < 0 is the NOSR form (no framing); opt the `optional` representation.  A packed
+// list's length prefix depends on its payload, so the measure pass sizes the payload first; the
+// write pass sizes it again from the same elements.  A NULL element (null byte 2) has no protobuf
+// form: the measure pass raises *bad and the host answers KHIP_E_UNSUPPORTED before anything is
+// written.
+
+// the varint of a sign-extended int32 / int64: 1..10 bytes
+__device__ __forceinline__ int pb_val_len(int type, const Val& v) {
+  return type == KHIP_TYPE_DOUBLE ? 8 : avro_varint_len((uint64_t)v.i);
+}
+__device__ __forceinline__ int pb_tag_len(int c) { return c + 1 < 16 ? 1 : 2; }  // field c + 1 <= 32
+// a scalar is on the wire: non-NULL, and not the all-zero default unless the field has presence
+__device__ __forceinline__ bool pb_present(const Val& v, int opt) { return !v.null && (opt || v.i != 0); }
+
+template <class W>
+__device__ __forceinline__ void put_pb_scalar(W& w, int type, const Val& v) {
+  if (type == KHIP_TYPE_DOUBLE) {
+#pragma unroll
+    for (int b = 0; b < 8; b++) w.put((uint8_t)((uint64_t)v.i >> (8 * b)));
+  } else {
+    put_avro_varint(w, (uint64_t)v.i);
+  }
+}
+
+// the payload bytes of row i's list in ARRAY column c; *cnt its length, *bad set on a NULL element
+__device__ __forceinline__ int64_t pb_list_payload(const SinkParams& q, const RowsDev& r, int64_t i, int c, int* cnt,
+                                                   bool* bad) {
+  int64_t len = 0;
+  Val v;
+  int e = 0;
+  for (; row_elem(q, r, i, c, e, v); e++) {
+    if (v.null) *bad = true;
+    len += pb_val_len(q.vtype[c], v);
+  }
+  *cnt = e;
+  return len;
+}
+
+template <bool ARR>
+__device__ __forceinline__ int64_t pb_value_len(const SinkParams& q, const RowsDev& r, int64_t i, int32_t schema_id,
+                                                int opt, bool* bad) {
+  int64_t len = schema_id >= 0 ? 6 : 0;
+  for (int c = 0; c < q.n_val; c++) {
+    if (ARR && q.varr[c] > 0) {
+      int cnt;
+      const int64_t pl = pb_list_payload(q, r, i, c, &cnt, bad);
+      if (cnt) len += pb_tag_len(c) + avro_varint_len((uint64_t)pl) + pl;
+      continue;
+    }
+    const Val v = row_value_val(q, r, i, c);
+    if (pb_present(v, opt)) len += pb_tag_len(c) + pb_val_len(q.vtype[c], v);
+  }
+  return len;
+}
+
+// vpayload(c, &cnt): the payload bytes and length of the row's list in ARRAY column c
+template <bool ARR, class W, class F, class P, class G>
+__device__ __forceinline__ void put_pb_value(W& w, const SinkParams& q, int32_t schema_id, int opt, F&& vval,
+                                             P&& vpayload, G&& velem) {
+  if (schema_id >= 0) {
+    w.put(0);
+    put_be(w, (uint64_t)(uint32_t)schema_id, 4);
+    w.put(0);  // the message-index list [0]
+  }
+  for (int i = 0; i < q.n_val; i++) {
+    const uint32_t fld = (uint32_t)(i + 1) << 3;
+    if (ARR && q.varr[i] > 0) {
+      int cnt = 0;
+      const int64_t pl = vpayload(i, &cnt);
+      if (!cnt) continue;
+      put_avro_varint(w, fld | 2);
+      put_avro_varint(w, (uint64_t)pl);
+      Val v;
+      for (int e = 0; e < cnt && velem(i, e, v); e++) put_pb_scalar(w, q.vtype[i], v);
+      continue;
+    }
+    const Val v = vval(i);
+    if (!pb_present(v, opt)) continue;
+    put_avro_varint(w, fld | (q.vtype[i] == KHIP_TYPE_DOUBLE ? 1u : 0u));
+    put_pb_scalar(w, q.vtype[i], v);
+  }
+}
+
+template <bool ARR>
+__global__ __launch_bounds__(256) void k_sink_measure_pb(const SinkParams* __restrict__ qp, RowsDev r, int64_t n,
+                                                         int kfix, int64_t nT, int64_t* __restrict__ klen,
+                                                         int64_t* __restrict__ vlen, int64_t* __restrict__ tsum,
+                                                         int32_t schema_id, int opt, int32_t* __restrict__ bad) {
+  __shared__ int64_t ws[2][4];
+  const SinkParams& q = *qp;
+  static_assert(SK_TR == 1, "one row per thread");
+  const int64_t i = (int64_t)blockIdx.x * SK_TILE + threadIdx.x;
+  int64_t sk = 0, sv = 0;
+  bool b = false;
+  if (i < n) {
+    if (!kfix) {
+      CountW kw;
+      encode_key_row(kw, q, r, i);
+      klen[i + 1] = sk = kw.n;
+    }
+    if (!value_is_null(q, r, i)) sv = pb_value_len<ARR>(q, r, i, schema_id, opt, &b);
+    vlen[i + 1] = sv;
+  }
+  if (ARR && b) atomicOr(bad, 1);
+  sk_block_sum2(sk, sv, ws);
+  if (threadIdx.x == 0) {
+    tsum[1 + blockIdx.x] = sk;
+    tsum[nT + 2 + blockIdx.x] = sv;
+  }
+}
+
+// k_sink_write_avro for PROTOBUF values.
+__global__ KHIP_SINK_WRITE_LB void k_sink_write_pb(const SinkParams* __restrict__ qp, RowsDev r, int64_t n, int kfix,
+                                                   int kwords, int64_t nT, const int64_t* __restrict__ tsum,
+                                                   int64_t* __restrict__ koff, uint8_t* __restrict__ kb,
+                                                   int64_t* __restrict__ voff, uint8_t* __restrict__ vb,
+                                                   uint8_t* __restrict__ vnull, int32_t schema_id, int opt) {
+  __shared__ int64_t ws[2][4];
+  __shared__ uint32_t vst[4][SK_WBUF / 4 + 4];
+  const SinkParams& q = *qp;
+  const int wave = threadIdx.x >> 6;
+  const int64_t i = (int64_t)blockIdx.x * SK_TILE + threadIdx.x;
+  const bool in = i < n;
+  const int64_t kl = !in ? 0 : kfix ? kfix : koff[i + 1];
+  const int64_t vl = in ? voff[i + 1] : 0;
+  int64_t ko = kl, vo = vl, tk, tv;
+  sk_block_scan2(ko, vo, tk, tv, ws);
+  ko += kfix ? (int64_t)blockIdx.x * SK_TILE * kfix : tsum[blockIdx.x];
+  vo += tsum[nT + 1 + blockIdx.x];
+  const int64_t wbase = __shfl(vo, 0, 64), wlen = __shfl(vo + vl, 63, 64) - wbase;  // past-n lanes: vl 0
+  const bool staged = wlen <= SK_WBUF;
+  const bool isnull = in ? value_is_null(q, r, i) : true;
+  Val v0{0, nullptr, 0, true}, v1 = v0, v2 = v0, v3 = v0;  // the first four value columns
+  if (!isnull) {
+    if (q.n_val > 0) v0 = row_value_val(q, r, i, 0);
+    if (q.n_val > 1) v1 = row_value_val(q, r, i, 1);
+    if (q.n_val > 2) v2 = row_value_val(q, r, i, 2);
+    if (q.n_val > 3) v3 = row_value_val(q, r, i, 3);
+  }
+  auto vget = [&](int c) {
+    return c == 0 ? v0 : c == 1 ? v1 : c == 2 ? v2 : c == 3 ? v3 : row_value_val(q, r, i, c);
+  };
+  auto no_payload = [](int, int*) { return (int64_t)0; };  // (a scalar sink has no ARRAY column)
+  auto no_elem = [](int, int, Val&) { return false; };
+  if (staged && !isnull && vl > 0) {
+    LdsW vw{(sk_lds_u8*)vst[wave] + (vo - wbase)};
+    put_pb_value<false>(vw, q, schema_id, opt, vget, no_payload, no_elem);
+  }
+  __syncthreads();
+  if (staged && wlen > 0) sk_wave_copy((const uint8_t*)vst[wave], (int)wlen, vb + wbase);
+  if (in) {
+    if (kwords) {
+      put_key_words(q, r, i, (uint64_t*)(kb + ko));
+    } else {
+      MemW kw{kb + ko};
+      encode_key_row(kw, q, r, i);
+    }
+    sk_st(vnull + i, (uint8_t)(isnull ? 1 : 0));
+    if (!staged && !isnull && vl > 0) {
+      MemW vw{vb + vo};
+      put_pb_value<false>(vw, q, schema_id, opt, vget, no_payload, no_elem);
+    }
+    sk_st(koff + i + 1, ko + kl);
+    sk_st(voff + i + 1, vo + vl);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    koff[0] = 0;
+    voff[0] = 0;
+  }
+}
+
+// k_sink_write_arr_avro for PROTOBUF values.
+__global__ KHIP_SINK_WRITE_LB void k_sink_write_arr_pb(const SinkParams* __restrict__ qp, RowsDev r, int64_t n,
+                                                       int kfix, int kwords, int64_t nT,
+                                                       const int64_t* __restrict__ tsum, int64_t* __restrict__ koff,
+                                                       uint8_t* __restrict__ kb, int64_t* __restrict__ voff,
+                                                       uint8_t* __restrict__ vb, uint8_t* __restrict__ vnull,
+                                                       int32_t schema_id, int opt) {
+  __shared__ int64_t ws[2][4];
+  __shared__ uint32_t ast[SK_ABUF / 4 + 4];
+  const SinkParams& q = *qp;
+  const int64_t i = (int64_t)blockIdx.x * SK_TILE + threadIdx.x;
+  const bool in = i < n;
+  const int64_t kl = !in ? 0 : kfix ? kfix : koff[i + 1];
+  const int64_t vl = in ? voff[i + 1] : 0;
+  int64_t ko = kl, vo = vl, tk, tv;
+  sk_block_scan2(ko, vo, tk, tv, ws);
+  ko += kfix ? (int64_t)blockIdx.x * SK_TILE * kfix : tsum[blockIdx.x];
+  const int64_t tbase = tsum[nT + 1 + blockIdx.x];  // the tile's first value byte; vo: the row's, within the tile
+  const bool isnull = in ? value_is_null(q, r, i) : true;
+  Val v0{0, nullptr, 0, true}, v1 = v0, v2 = v0, v3 = v0;  // the first four value columns (scalars)
+  if (!isnull) {
+    if (q.n_val > 0 && !q.varr[0]) v0 = row_value_val(q, r, i, 0);
+    if (q.n_val > 1 && !q.varr[1]) v1 = row_value_val(q, r, i, 1);
+    if (q.n_val > 2 && !q.varr[2]) v2 = row_value_val(q, r, i, 2);
+    if (q.n_val > 3 && !q.varr[3]) v3 = row_value_val(q, r, i, 3);
+  }
+  auto vget = [&](int c) {
+    return c == 0 ? v0 : c == 1 ? v1 : c == 2 ? v2 : c == 3 ? v3 : row_value_val(q, r, i, c);
+  };
+  const uint8_t* als = (const uint8_t*)ast;
+  for (int64_t lo = 0; lo < tv; lo += SK_ABUF) {
+    if (!isnull && vo < lo + SK_ABUF && vo + vl > lo) {
+      WinW vw{(sk_lds_u8*)ast, vo - lo};
+      put_pb_value<true>(vw, q, schema_id, opt, vget,
+                         [&](int c, int* cnt) {
+                           bool bad = false;
+                           return pb_list_payload(q, r, i, c, cnt, &bad);
+                         },
+                         [&](int c, int e, Val& v) { return row_elem(q, r, i, c, e, v); });
+    }
+    __syncthreads();
+    sk_range_copy<256>(als, (int)(tv - lo < SK_ABUF ? tv - lo : SK_ABUF), vb + tbase + lo, threadIdx.x);
+    __syncthreads();
+  }
+  if (in) {
+    if (kwords) {
+      put_key_words(q, r, i, (uint64_t*)(kb + ko));
+    } else {
+      MemW kw{kb + ko};
+      encode_key_row(kw, q, r, i);
+    }
+    sk_st(vnull + i, (uint8_t)(isnull ? 1 : 0));
+    sk_st(koff + i + 1, ko + kl);
+    sk_st(voff + i + 1, tbase + vo + vl);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    koff[0] = 0;
+    voff[0] = 0;
+  }
+}
+
 // ------------------------------------------------------------------ GROUP BY columns → key bytes
 
 struct KeySrcDev {
@@ -1250,7 +1487,10 @@ struct khip_sink {
   SinkParams q{};
   int device = 0;
   bool has_arr = false;        // some value column is an ARRAY: the k_sink_*<true> / _arr kernels
-  int32_t avro_id = -1;        // AVRO values: the schema id of the records' header; -1 = not set yet
+  int32_t avro_id = -1;        // AVRO / PROTOBUF values: the schema id of the records' header; -1 = not set yet
+  bool pb = false;             // PROTOBUF / PROTOBUF_NOSR values: the k_sink_*_pb kernels
+  int pb_opt = 0;              // KHIP_PROTO_OPTIONAL: scalars have presence
+  DevBuf pb_bad;               // the measure pass's flag: some list holds a NULL element
   int32_t src_len[SK_MAX] = {};  // per rows column: its ARRAY length L, 0 = scalar
   hipStream_t stream = nullptr;
   DevBuf dq, bsum, bsum2, tsum, koff, kbytes, kvalid, voff, vbytes, vnull;
@@ -1300,11 +1540,16 @@ extern "C" {
 khip_status khip_sink_create(const khip_sink_desc* d, khip_sink** out) {
   clear_error();
   if (!d || !out) return fail(KHIP_E_INVALID, "null argument");
-  const int kf = d->key_format, vf = d->value_format;
+  const int kf = d->key_format;
+  int vf = d->value_format;
+  const bool pb_opt = vf > 0 && (vf & KHIP_PROTO_OPTIONAL);
+  if (pb_opt) vf &= ~KHIP_PROTO_OPTIONAL;
+  const bool pb = vf == KHIP_FMT_PROTOBUF || vf == KHIP_FMT_PROTOBUF_NOSR;
   if (kf != KHIP_FMT_KAFKA && kf != KHIP_FMT_JSON && kf != KHIP_FMT_DELIMITED)
     return fail(KHIP_E_UNSUPPORTED, "sink key format (KAFKA, JSON, DELIMITED)");
-  if (vf != KHIP_FMT_KAFKA && vf != KHIP_FMT_JSON && vf != KHIP_FMT_DELIMITED && vf != KHIP_FMT_AVRO)
-    return fail(KHIP_E_UNSUPPORTED, "sink value format (KAFKA, JSON, DELIMITED, AVRO)");
+  if (vf != KHIP_FMT_KAFKA && vf != KHIP_FMT_JSON && vf != KHIP_FMT_DELIMITED && vf != KHIP_FMT_AVRO && !pb)
+    return fail(KHIP_E_UNSUPPORTED, "sink value format (KAFKA, JSON, DELIMITED, AVRO, PROTOBUF, PROTOBUF_NOSR)");
+  if (pb_opt && !pb) return fail(KHIP_E_INVALID, "KHIP_PROTO_OPTIONAL belongs to the PROTOBUF value formats");
   if (d->n_key_cols < 1 || d->n_key_cols > SK_MAX || !d->key_types) return fail(KHIP_E_INVALID, "1..32 key columns");
   if (kf == KHIP_FMT_KAFKA && d->n_key_cols != 1)
     return fail(KHIP_E_UNSUPPORTED, "the KAFKA key format carries one column");
@@ -1314,6 +1559,8 @@ khip_status khip_sink_create(const khip_sink_desc* d, khip_sink** out) {
   if (d->window_kind < KHIP_WINDOW_NONE || d->window_kind > KHIP_WINDOW_SESSION) return fail(KHIP_E_INVALID, "window kind");
   khip_sink* s = new khip_sink();
   s->desc = *d;
+  s->pb = pb;
+  s->pb_opt = pb_opt ? 1 : 0;
   SinkParams& q = s->q;
   q.key_format = kf;
   q.value_format = vf;
@@ -1350,9 +1597,9 @@ khip_status khip_sink_create(const khip_sink_desc* d, khip_sink** out) {
     q.vtype[i] = d->value_types[i] & 0xFFFF;
     q.varr[i] = d->value_types[i] >> 16;  // KHIP_SINK_ARRAY(L): 1..32767, 0 = scalar
     q.vsrc[i] = d->value_src[i];
-    if (q.varr[i] && vf != KHIP_FMT_JSON && vf != KHIP_FMT_AVRO) {
+    if (q.varr[i] && vf != KHIP_FMT_JSON && vf != KHIP_FMT_AVRO && !pb) {
       delete s;
-      return fail(KHIP_E_INVALID, "an ARRAY value column needs the JSON or AVRO value format (KAFKA / DELIMITED carry no arrays)");
+      return fail(KHIP_E_INVALID, "an ARRAY value column needs the JSON or AVRO value format, or PROTOBUF / PROTOBUF_NOSR (KAFKA / DELIMITED carry no arrays)");
     }
     if (q.varr[i] && (q.vsrc[i] == KHIP_SINK_SRC_WS || q.vsrc[i] == KHIP_SINK_SRC_WE)) {
       delete s;
@@ -1415,6 +1662,16 @@ khip_status khip_sink_set_avro_schema_id(khip_sink* s, int32_t schema_id) {
   clear_error();
   if (!s) return fail(KHIP_E_INVALID, "null argument");
   if (s->q.value_format != KHIP_FMT_AVRO) return fail(KHIP_E_INVALID, "a schema id belongs to the AVRO value format");
+  if (schema_id < 0) return fail(KHIP_E_INVALID, "negative schema id");
+  s->avro_id = schema_id;
+  return KHIP_OK;
+}
+
+khip_status khip_sink_set_schema_id(khip_sink* s, int32_t schema_id) {
+  clear_error();
+  if (!s) return fail(KHIP_E_INVALID, "null argument");
+  if (s->q.value_format != KHIP_FMT_AVRO && s->q.value_format != KHIP_FMT_PROTOBUF)
+    return fail(KHIP_E_INVALID, "a schema id belongs to the AVRO and PROTOBUF value formats");
   if (schema_id < 0) return fail(KHIP_E_INVALID, "negative schema id");
   s->avro_id = schema_id;
   return KHIP_OK;
@@ -1499,6 +1756,9 @@ khip_status khip_sink_encode(khip_sink* s, const khip_sink_rows* rows, khip_sink
   const SinkParams& q = s->q;
   const bool avro = q.value_format == KHIP_FMT_AVRO;
   if (avro && s->avro_id < 0) return fail(KHIP_E_STATE, "AVRO values need khip_sink_set_avro_schema_id first");
+  if (q.value_format == KHIP_FMT_PROTOBUF && s->avro_id < 0)
+    return fail(KHIP_E_STATE, "PROTOBUF values need khip_sink_set_schema_id first");
+  const int32_t pb_id = q.value_format == KHIP_FMT_PROTOBUF ? s->avro_id : -1;  // NOSR: no framing
   const int64_t n = rows->n_rows;
   if (n < 0 || !out->key_offsets || !out->value_offsets || !out->value_null) return fail(KHIP_E_INVALID, "rows / outputs");
   const bool windowed = q.window_kind != KHIP_WINDOW_NONE;
@@ -1590,7 +1850,13 @@ khip_status khip_sink_encode(khip_sink* s, const khip_sink_rows* rows, khip_sink
   if (n) {
     KHIP_TRY(s->tsum.ensure((size_t)(2 * (nT + 1)) * 8));
     int64_t* ts = s->tsum.as<int64_t>();
-    if (avro)
+    if (s->pb) {
+      KHIP_TRY(s->pb_bad.ensure(8));
+      if (s->has_arr) KHIP_TRY_HIP(hipMemsetAsync(s->pb_bad.p, 0, 8, s->stream));
+      hipLaunchKernelGGL(s->has_arr ? k_sink_measure_pb<true> : k_sink_measure_pb<false>, dim3((unsigned)nT), dim3(256), 0,
+                         s->stream, s->dq.as<SinkParams>(), r, n, kfix, nT, koff, voff, ts, pb_id, s->pb_opt,
+                         s->pb_bad.as<int32_t>());
+    } else if (avro)
       hipLaunchKernelGGL(s->has_arr ? k_sink_measure_avro<true> : k_sink_measure_avro<false>, dim3((unsigned)nT), dim3(256), 0,
                          s->stream, s->dq.as<SinkParams>(), r, n, kfix, nT, koff, voff, ts);
     else
@@ -1598,8 +1864,12 @@ khip_status khip_sink_encode(khip_sink* s, const khip_sink_rows* rows, khip_sink
                          s->dq.as<SinkParams>(), r, n, kfix, nT, koff, voff, ts);
     KHIP_TRY_HIP(hipGetLastError());
     int64_t tk = 0, tv = 0;
+    int32_t bad = 0;
+    if (s->pb && s->has_arr) KHIP_TRY_HIP(hipMemcpyAsync(&bad, s->pb_bad.p, 4, hipMemcpyDeviceToHost, s->stream));
     if (!kfix) KHIP_TRY(sk_scan(s, s->bsum, ts, nT, &tk, false));
     KHIP_TRY(sk_scan(s, s->bsum2, ts + nT + 1, nT, &tv, true));
+    if (bad)
+      return fail(KHIP_E_UNSUPPORTED, "a NULL array element has no PROTOBUF form (the query stays with the reference)");
     ktot = kfix ? (int64_t)kfix * n : tk;
     vtot = tv;
   } else {
@@ -1626,7 +1896,11 @@ khip_status khip_sink_encode(khip_sink* s, const khip_sink_rows* rows, khip_sink
   }
   if (n) {
     const int kwords = kfix && q.ktype[0] == KHIP_TYPE_INT64 && ((uintptr_t)kb & 7) == 0 ? kfix / 8 : 0;
-    if (avro)
+    if (s->pb)
+      hipLaunchKernelGGL(s->has_arr ? k_sink_write_arr_pb : k_sink_write_pb, dim3((unsigned)nT), dim3(256), 0, s->stream,
+                         s->dq.as<SinkParams>(), r, n, kfix, kwords, nT, s->tsum.as<int64_t>(), koff, kb, voff, vb, vn,
+                         pb_id, s->pb_opt);
+    else if (avro)
       hipLaunchKernelGGL(s->has_arr ? k_sink_write_arr_avro : k_sink_write_avro, dim3((unsigned)nT), dim3(256), 0, s->stream,
                          s->dq.as<SinkParams>(), r, n, kfix, kwords, nT, s->tsum.as<int64_t>(), koff, kb, voff, vb, vn,
                          s->avro_id);
@@ -1659,7 +1933,7 @@ khip_status khip_sink_destroy(khip_sink* s) {
   DeviceGuard g(s->device);
   if (s->stream) hipStreamSynchronize(s->stream);
   DevBuf* bufs[] = {&s->dq, &s->bsum, &s->bsum2, &s->tsum, &s->koff, &s->kbytes, &s->kvalid, &s->voff, &s->vbytes, &s->vnull, &s->st_key,
-                    &s->st_koff, &s->st_kbytes, &s->st_ws, &s->st_we, &s->st_tomb};
+                    &s->st_koff, &s->st_kbytes, &s->st_ws, &s->st_we, &s->st_tomb, &s->pb_bad};
   for (DevBuf* b : bufs) b->release();
   for (int c = 0; c < SK_MAX; c++) {
     s->st_col[c].release();

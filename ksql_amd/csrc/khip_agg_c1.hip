@@ -39,6 +39,8 @@
 //                 base + a 32-bit offset); (key - kmin, window) → a 32-bit identity when
 //                 it fits (no key hash on the record path), LDS identity CAS + u32 row-time max +
 //                 u32 count, claimed entries listed (the write-out walks the list, not the table);
+//                 a last chunk of one or two live slot rows runs a variant that issues nothing
+//                 for the other rows; a partition without resident rows skips the count pass;
 //                 resident rows merged, closed rows evicted, HAVING counts and changelog flags
 //                 maintained exactly as k_part_merge_c1 does (k_part_commit publishes)
 //
@@ -1307,12 +1309,14 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
     // CASes are issued (prefetch): the chunk's segment lookups and the table-full flag then return
     // with the CASes (LDS returns in order), not behind this chunk's plane atomics, and the loads
     // have a whole chunk to land.  Returns false when the table is (about to be) full.
-    auto apply = [&](const uint64_t (&xr)[AU], const uint32_t (&txr)[AU], uint32_t l0, auto R32, auto&& prefetch) -> bool {
-      ID id[AU];
-      uint32_t e[AU], tr[AU];
-      bool pend[AU], claimed[AU];
+    auto apply = [&](const uint64_t (&xr)[AU], const uint32_t (&txr)[AU], uint32_t l0, auto R32, auto NUc,
+                     auto&& prefetch) -> bool {
+      constexpr int NU = decltype(NUc)::value;  // live slot rows: AU, or a last chunk's 1 or 2
+      ID id[NU];
+      uint32_t e[NU], tr[NU];
+      bool pend[NU], claimed[NU];
 #pragma unroll
-      for (int u = 0; u < AU; u++) {
+      for (int u = 0; u < NU; u++) {
         const uint32_t li = l0 + threadIdx.x + (uint32_t)(u * NT);
         const uint64_t v = xr[u];
         const int32_t t32 = WIDE ? (int32_t)txr[u] : (int32_t)(uint32_t)v;
@@ -1331,9 +1335,9 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
         e[u] = act ? h >> (32 - log2H) : dummy;
         tr[u] = (uint32_t)(t32 - tmin32) + 1u;
       }
-      ID old[AU];
+      ID old[NU];
 #pragma unroll
-      for (int u = 0; u < AU; u++) {
+      for (int u = 0; u < NU; u++) {
         old[u] = EMPTY;
         __hip_atomic_compare_exchange_strong(&ids[e[u]], &old[u], id[u], __ATOMIC_RELAXED, __ATOMIC_RELAXED,
                                              __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1342,24 +1346,24 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
       prefetch();
       const int full = __builtin_amdgcn_readfirstlane(fullv);  // (one LDS word: the same in every lane)
 #pragma unroll
-      for (int u = 0; u < AU; u++) {
+      for (int u = 0; u < NU; u++) {
         claimed[u] = id[u] != EMPTY && old[u] == EMPTY;
         pend[u] = old[u] != EMPTY && old[u] != id[u];
       }
       for (int probes = 1;; probes++) {  // collisions: every pending record probes on together
         bool anyp = false;
 #pragma unroll
-        for (int u = 0; u < AU; u++) anyp |= pend[u];
+        for (int u = 0; u < NU; u++) anyp |= pend[u];
         if (!__ballot(anyp)) break;
         if (probes >= H) {
           lovf = 1;
 #pragma unroll
-          for (int u = 0; u < AU; u++)
+          for (int u = 0; u < NU; u++)
             if (pend[u]) id[u] = EMPTY;
           break;
         }
 #pragma unroll
-        for (int u = 0; u < AU; u++) {
+        for (int u = 0; u < NU; u++) {
           if (!pend[u]) continue;
           e[u] = (e[u] + 1) & (uint32_t)(H - 1);
           ID o2 = EMPTY;
@@ -1371,13 +1375,13 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
       }
       int nnow;
       {
-        bool cl[AU];
+        bool cl[NU];
 #pragma unroll
-        for (int u = 0; u < AU; u++) cl[u] = claimed[u] && id[u] != EMPTY;
-        nnow = mg_list_append_n<AU>(cl, e, list, &nnew);
+        for (int u = 0; u < NU; u++) cl[u] = claimed[u] && id[u] != EMPTY;
+        nnow = mg_list_append_n<NU>(cl, e, list, &nnew);
       }
 #pragma unroll
-      for (int u = 0; u < AU; u++) {
+      for (int u = 0; u < NU; u++) {
         if (id[u] == EMPTY) continue;
         __hip_atomic_fetch_max(&rt[e[u]], tr[u], WG_RLX);
         __hip_atomic_fetch_add(&ct[e[u]], 1u, WG_RLX);
@@ -1386,27 +1390,69 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
     };
     constexpr uint32_t CR = (uint32_t)(AU * NT);  // records per chunk
     const uint32_t nch = (rn + CR - 1u) / CR;
+    // The last chunk has nu = ceil((rn - l0) / NT) live slot rows (records u NT + thread of the
+    // chunk, nu uniform like rn).  With nu = 1 or 2 it is applied after the loop by a variant that
+    // issues nothing for the rows u >= nu: no identity, CAS, probe, append or plane atomic.  (Its
+    // prefetch stays the full load, dead rows clamped to the last record: sized loads were
+    // measured and cost more than they saved, profiles/c1_merge_tail.)  nu >= 3 takes the full code.
+    constexpr int TAILNU = AU - 1 < 2 ? AU - 1 : 2;  // the largest nu with a variant of its own
+    const uint32_t tail_r = rn - (nch - 1u) * CR;    // (rn > 0) records of the last chunk
+    const uint32_t tnu =
+        rn > 0 && tail_r <= (uint32_t)(TAILNU * NT) ? (tail_r + (uint32_t)(NT - 1)) / (uint32_t)NT : (uint32_t)AU;
+    const uint32_t nfc = tnu < (uint32_t)AU ? nch - 1u : nch;
+    using FullNU = std::integral_constant<int, AU>;
     if (rn > 0) {  // chunks 0 and 1 are in flight (load01); each set is reloaded as it is applied
-      for (uint32_t c = 0; c < nch; c += 2) {
+      bool go = true;
+      for (uint32_t c = 0; c < nfc; c += 2) {
         auto pa = [&] { if (c + 2 < nch) load(ra, ta, (c + 2) * CR, it); };
-        const bool ga = r32 ? apply(ra, ta, c * CR, std::true_type{}, pa) : apply(ra, ta, c * CR, std::false_type{}, pa);
-        if (!ga || c + 1 >= nch) break;
+        const bool ga = r32 ? apply(ra, ta, c * CR, std::true_type{}, FullNU{}, pa)
+                            : apply(ra, ta, c * CR, std::false_type{}, FullNU{}, pa);
+        if (!ga) go = false;
+        if (!ga || c + 1 >= nfc) break;
         auto pb = [&] { if (c + 3 < nch) load(rb, tb, (c + 3) * CR, it); };
-        const bool gb = r32 ? apply(rb, tb, (c + 1) * CR, std::true_type{}, pb)
-                            : apply(rb, tb, (c + 1) * CR, std::false_type{}, pb);
-        if (!gb) break;
+        const bool gb = r32 ? apply(rb, tb, (c + 1) * CR, std::true_type{}, FullNU{}, pb)
+                            : apply(rb, tb, (c + 1) * CR, std::false_type{}, FullNU{}, pb);
+        if (!gb) {
+          go = false;
+          break;
+        }
+      }
+      if (go && nfc < nch) {  // the short last chunk, from the set that holds it
+        auto tail = [&](const uint64_t (&xr)[AU], const uint32_t (&txr)[AU], auto NUc) {
+          auto none = [] {};
+          if (r32) apply(xr, txr, nfc * CR, std::true_type{}, NUc, none);
+          else apply(xr, txr, nfc * CR, std::false_type{}, NUc, none);
+        };
+        using N1 = std::integral_constant<int, 1>;
+        using N2 = std::integral_constant<int, TAILNU>;
+        if (nfc & 1u) {
+          if (tnu == 1u) tail(rb, tb, N1{});
+          else tail(rb, tb, N2{});
+        } else {
+          if (tnu == 1u) tail(ra, ta, N1{});
+          else tail(ra, ta, N2{});
+        }
       }
     }
     lds_barrier();
-    // the item's records are in the table (its segments are no longer read): the next item's
-    // segments and first chunks now
+    // the item's records are in the table (its segments are no longer read).  Every thread takes
+    // the list's length and the overflow flag now: the barriers of the next item's prep then
+    // separate these reads from thread 0's reset, and the item's closing barrier the reset from
+    // the next item's appends.  (The workgroup's last item resets nothing: nothing reads it.)
+    const int nnew_r = __builtin_amdgcn_readfirstlane(nnew);
+    const int lovf_r = __builtin_amdgcn_readfirstlane(lovf);
+    // the next item's segments and first chunks
     if (wn < nwork) {
       prep(pr, nx);
+      if (threadIdx.x == 0) {
+        lovf = 0;
+        nnew = 0;
+      }
       load01(nx);
     }
     C1M_T(1);
-    const int nl = nnew < H ? nnew : H;
-    if (lovf || nnew > q.hmax) {  // more groups than the table takes: retried with 2x sub-passes
+    const int nl = nnew_r < H ? nnew_r : H;
+    if (lovf_r || nnew_r > q.hmax) {  // more groups than the table takes: retried with 2x sub-passes
       if (threadIdx.x == 0) fail[p] |= 1;
       for (int i = threadIdx.x; i < nl; i += NT) {
         const uint32_t e = list[i];
@@ -1415,12 +1461,7 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
         ct[e] = 0u;
       }
       evict_failed();
-      lds_barrier();
-      if (threadIdx.x == 0) {
-        lovf = 0;
-        nnew = 0;
-      }
-      lds_barrier();
+      lds_barrier();  // the table is clear for the next item
       continue;
     }
     // 2. resident rows: mark the delta entries they absorb; count live and closed rows
@@ -1445,44 +1486,64 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
     // the wave's share of the list: new (unmatched) entries
     const int per = ((nl + NW - 1) / NW + 63) & ~63;
     const int lb0 = wave * per, lb1 = lb0 + per < nl ? lb0 + per : nl;
-    int nnw = 0;
-    for (int k = lb0; k < lb1; k += 64) {
-      const int i = k + lane;
-      const uint32_t e = i < lb1 ? list[i] : dummy;
-      const bool isnew = i < lb1 && !(rt[e] & RT_MATCHED);
-      nnw += (int)__popcll(__ballot(isnew));
-    }
     // 3. per-wave row counts → the partition's region range (one atomic per work item), and the
     //    closed store's slots for its closed rows
-    const int wave_rows = (int)wave_sum(n_mine) + nnw;
-    const int wave_cl = (int)wave_sum(n_cl);
-    if (lane == 0) {
-      wsum[wave] = wave_rows;
-      csum[wave] = wave_cl;
-    }
-    lds_barrier();
     int wave_before = 0, total = 0, cl_before = 0, cl_total = 0;
-    for (int k = 0; k < NW; k++) {
-      if (k < wave) wave_before += wsum[k], cl_before += csum[k];
-      total += wsum[k];
-      cl_total += csum[k];
-    }
-    if (threadIdx.x == 0) {
-      if (work) lbase = total ? atomicAdd(&newcnt[p], (unsigned long long)total) : 0ULL;
-      else {
-        lbase = 0;
-        newcnt[p] = (unsigned long long)total;
+    unsigned long long lb, cb;  // the item's base in the region and in the closed store
+    if (nrow == 0) {
+      // no resident rows (uniform): nothing is matched, so every listed entry is a new row and the
+      // counts are known without walking the list: the wave's rows are its share, the waves
+      // before it hold min(lb0, nl), no row is closed (no closed-store slots)
+      total = nl;
+      wave_before = lb0 < nl ? lb0 : nl;
+      cb = 0ULL;
+      if (work) {  // a retry's sub-passes share the region: thread 0 reserves, everyone reads
+        if (threadIdx.x == 0) lbase = total ? atomicAdd(&newcnt[p], (unsigned long long)total) : 0ULL;
+        lds_barrier();
+        lb = lbase;
+      } else {
+        lb = 0ULL;
+        if (threadIdx.x == 0) newcnt[p] = (unsigned long long)total;
       }
-      // (an item that does not fit its region reserves with its own copy, evict_failed)
-      cbase = (int64_t)(lbase + total) <= q.cmax
-                  ? c1_reserve_closed(closed_n, (unsigned long long)cl_total, closed_cap, &fail[p], need)
-                  : 0ULL;
+    } else {
+      int nnw = 0;
+      for (int k = lb0; k < lb1; k += 64) {
+        const int i = k + lane;
+        const uint32_t e = i < lb1 ? list[i] : dummy;
+        const bool isnew = i < lb1 && !(rt[e] & RT_MATCHED);
+        nnw += (int)__popcll(__ballot(isnew));
+      }
+      const int wave_rows = (int)wave_sum(n_mine) + nnw;
+      const int wave_cl = (int)wave_sum(n_cl);
+      if (lane == 0) {
+        wsum[wave] = wave_rows;
+        csum[wave] = wave_cl;
+      }
+      lds_barrier();
+      for (int k = 0; k < NW; k++) {
+        if (k < wave) wave_before += wsum[k], cl_before += csum[k];
+        total += wsum[k];
+        cl_total += csum[k];
+      }
+      if (threadIdx.x == 0) {
+        if (work) lbase = total ? atomicAdd(&newcnt[p], (unsigned long long)total) : 0ULL;
+        else {
+          lbase = 0;
+          newcnt[p] = (unsigned long long)total;
+        }
+        // (an item that does not fit its region reserves with its own copy, evict_failed)
+        cbase = (int64_t)(lbase + total) <= q.cmax
+                    ? c1_reserve_closed(closed_n, (unsigned long long)cl_total, closed_cap, &fail[p], need)
+                    : 0ULL;
+      }
+      lds_barrier();
+      lb = lbase;
+      cb = cbase;
     }
-    lds_barrier();
-    if ((int64_t)(lbase + total) > q.cmax) {
+    if ((int64_t)(lb + total) > q.cmax) {
       if (threadIdx.x == 0) {
         fail[p] |= 2;
-        atomicMax(need, (unsigned long long)(lbase + total));
+        atomicMax(need, (unsigned long long)(lb + total));
       }
       for (int i = threadIdx.x; i < nl; i += NT) {
         const uint32_t e = list[i];
@@ -1491,17 +1552,15 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
         ct[e] = 0u;
       }
       evict_failed();
-      lds_barrier();
-      if (threadIdx.x == 0) nnew = 0;
-      lds_barrier();
+      lds_barrier();  // the table is clear for the next item
       continue;
     }
     C1M_T(3);
     // 4. write: resident rows (merged), then the wave's new entries (ballot ranks: consecutive rows)
     uint64_t* dst0 = (isel ? buf0 : buf1) + (uint64_t)p * q.cmax * q.sw;
-    uint64_t cur = lbase + (uint64_t)wave_before;
-    uint64_t ccur = cbase + (uint64_t)cl_before;
-    const bool cmove = first && cbase != C1_NOSLOT;  // closed rows are copied (else only dropped)
+    uint64_t cur = lb + (uint64_t)wave_before;
+    uint64_t ccur = cb + (uint64_t)cl_before;
+    const bool cmove = first && cb != C1_NOSLOT;  // closed rows are copied (else only dropped)
     const uint64_t lt = (1ULL << lane) - 1;
     int nh = 0, nhc = 0;
     for (int64_t r0 = wave * 64; r0 < nrow; r0 += NT) {
@@ -1590,10 +1649,8 @@ __global__ __launch_bounds__(NT, 4) void k_c1_merge(
       if (lane == 0 && nh) atomicAdd(&hnew[p], (unsigned long long)nh);
       if (lane == 0 && nhc) atomicAdd(hclosed, (unsigned long long)nhc);
     }
-    lds_barrier();  // the table is clear for the next item
+    lds_barrier();  // the table is clear for the next item (its list length was reset after prep)
     C1M_T(4);
-    if (threadIdx.x == 0) nnew = 0;
-    lds_barrier();
   }
 }
 

@@ -11,12 +11,12 @@
 // tile's lengths in the block, adds the tile's carry and writes each record at its offset, and
 // the offsets.  A KAFKA INT32 / BIGINT key has a fixed width (no key lengths; a BIGINT key and its
 // window suffix leave as 8-byte words), and a JSON column's '{' / ',' + escaped name + ':' is built
-// once on the host.  A sink with an ARRAY value column (KHIP_SINK_ARRAY: JSON lists) runs its own
-// instantiations, k_sink_measure<true> and k_sink_write_arr; a scalar sink's kernels carry none
-// of it.  PROTOBUF values likewise run three kernels of their own ("the PROTOBUF sink's kernels").
-// A sink with AVRO values (the Confluent wire format of ksqlDB's own schema: scalars and
-// ARRAY columns, keys as above) runs three kernels of its own, "the AVRO sink's kernels" below: the
-// lengths in closed form, the same two stages on the way out.  Doubles print
+// once on the host.  The three kernels are templates over the value encoder ("the value encoders"
+// below): TextEnc for JSON / DELIMITED / KAFKA values, AvroEnc for AVRO values (the Confluent wire
+// format of ksqlDB's own schema: scalars and ARRAY columns, keys as above; the lengths in closed
+// form) and PbEnc for PROTOBUF / PROTOBUF_NOSR values.  A sink with an ARRAY value column
+// (KHIP_SINK_ARRAY) runs its own instantiations, k_sink_measure<Enc, true> and
+// k_sink_write_arr<Enc>; a scalar sink's kernels carry none of it.  Doubles print
 // through the Schubfach shortest-decimal algorithm (R. Giulietti 2020; java.lang.Double.toString
 // since JDK 19) with the 126-bit powers of ten of tools/gen_dtoa.py, so every digit is computed
 // exactly with 64-bit integer arithmetic.  Byte parity of DOUBLE text therefore assumes the
@@ -77,6 +77,7 @@ struct CountW {
 struct MemW {
   uint8_t* p;
   __device__ __forceinline__ void put(uint8_t c) { *p++ = c; }
+  __device__ __forceinline__ static MemW at(uint32_t* stage, int64_t off) { return MemW{(uint8_t*)stage + off}; }
 };
 struct HostW {  // host: a JSON column prefix (SinkParams::kpre / vpre)
   uint8_t* p;
@@ -498,9 +499,8 @@ __device__ __forceinline__ void put_value(W& w, const SinkParams& q, F&& vval, G
 //
 // The Confluent wire format of the record ksqlDB's own schema describes (include/ksqldb_hip.h,
 // "AVRO values"): byte 0, the schema id big-endian, then per column the union ["null", T] — branch
-// 0 for NULL, branch 1 (the byte 0x02) and the value.  The AVRO sink runs kernels of its own
-// (k_sink_measure_avro, k_sink_write_avro, k_sink_write_arr_avro): put_value and the kernels of the
-// other formats carry none of this.
+// 0 for NULL, branch 1 (the byte 0x02) and the value.  An AVRO sink runs the kernels' AvroEnc
+// instantiations: put_value and the other formats' instantiations carry none of this.
 
 __device__ __forceinline__ uint64_t avro_zz(int64_t v) { return ((uint64_t)v << 1) ^ (uint64_t)(v >> 63); }
 // bytes of the varint of u: seven bits a byte
@@ -649,14 +649,13 @@ __device__ __forceinline__ bool value_is_null(const SinkParams& q, const RowsDev
 // Tiles of SK_TILE = 256 rows, one block of 256 threads, one row per thread (eight rows per
 // thread in rounds, measured earlier, kept the write pass's row state live across rounds: 171
 // VGPRs).
-constexpr int SK_TR = 1;
+constexpr int SK_TILE = 256;
 // k_sink_write at 4 waves per SIMD (<= 128 VGPRs; the spills are in the DOUBLE printer): 782-802
 // us per 22M rows against 840 at 5 and 890 uncapped (138 VGPRs), profiles/r05/ab/sink_two_pass.txt
 #ifndef KHIP_SINK_MINB
 #define KHIP_SINK_MINB 4
 #endif
 #define KHIP_SINK_WRITE_LB __launch_bounds__(256, KHIP_SINK_MINB)
-constexpr int SK_TILE = 256 * SK_TR;
 
 // Sums of (a, b) over the block; every thread gets them.
 __device__ __forceinline__ void sk_block_sum2(int64_t& a, int64_t& b, int64_t (*ws)[4]) {
@@ -702,40 +701,6 @@ __device__ __forceinline__ void sk_block_scan2(int64_t& a, int64_t& b, int64_t& 
   __syncthreads();
   a = pa + ia - a;
   b = pb + ib - b;
-}
-
-// Pass 1: each row's key / value length at klen / vlen[i + 1] (keys skipped when every key is kfix
-// bytes), each tile's sums at tsum[1 + tile] (keys) and tsum[nT + 2 + tile] (values).
-template <bool ARR>
-__global__ __launch_bounds__(256) void k_sink_measure(const SinkParams* __restrict__ qp, RowsDev r, int64_t n, int kfix,
-                                                      int64_t nT, int64_t* __restrict__ klen, int64_t* __restrict__ vlen,
-                                                      int64_t* __restrict__ tsum) {
-  __shared__ int64_t ws[2][4];
-  const SinkParams& q = *qp;
-  const int64_t base = (int64_t)blockIdx.x * SK_TILE;
-  int64_t sk = 0, sv = 0;
-#pragma unroll 1
-  for (int u = 0; u < SK_TR; u++) {
-    const int64_t i = base + u * 256 + threadIdx.x;
-    if (i >= n) break;
-    if (!kfix) {
-      CountW kw;
-      encode_key_row(kw, q, r, i);
-      klen[i + 1] = kw.n;
-      sk += kw.n;
-    }
-    CountW vw;
-    if (!value_is_null(q, r, i))
-      put_value<ARR>(vw, q, [&](int c) { return row_value_val(q, r, i, c); },
-                     [&](int c, int e, Val& v) { return row_elem(q, r, i, c, e, v); });
-    vlen[i + 1] = vw.n;
-    sv += vw.n;
-  }
-  sk_block_sum2(sk, sv, ws);
-  if (threadIdx.x == 0) {
-    tsum[1 + blockIdx.x] = sk;
-    tsum[nT + 2 + blockIdx.x] = sv;
-  }
 }
 
 // A fixed-width KAFKA BIGINT key and its window suffix as big-endian 8-byte words (kb + 8-aligned),
@@ -806,147 +771,10 @@ __device__ __forceinline__ void sk_range_copy(const uint8_t* lds, int L, uint8_t
 
 constexpr int SK_WBUF = 2048;  // staged value bytes per wave: 64 rows of 32
 
-
-// Pass 2 (after sk_scan made tsum the tiles' offsets): the tile scans its rows' lengths in the
-// block and adds its carry.  A wave whose 64 values take at most SK_WBUF bytes (one contiguous
-// range of the output) encodes them into LDS at their places in that range and copies the range
-// out in 16-byte stores (sk_wave_copy); a longer wave writes each value at its offset byte by byte.
-// Every load of a row comes before its first global store (on gfx950 a load behind a store waits
-// for the store).  Each row's end offsets go over its own length slots (koff / voff[i + 1]: only
-// this thread reads them, so no other tile's lengths are overwritten before they are read).
-// kwords: the key as kfix / 8 words.
-__global__ KHIP_SINK_WRITE_LB void k_sink_write(const SinkParams* __restrict__ qp, RowsDev r, int64_t n, int kfix,
-                                                    int kwords, int64_t nT, const int64_t* __restrict__ tsum,
-                                                    int64_t* __restrict__ koff, uint8_t* __restrict__ kb,
-                                                    int64_t* __restrict__ voff, uint8_t* __restrict__ vb,
-                                                    uint8_t* __restrict__ vnull) {
-  __shared__ int64_t ws[2][4];
-  __shared__ uint32_t vst[4][SK_WBUF / 4 + 4];
-  const SinkParams& q = *qp;
-  const int wave = threadIdx.x >> 6;
-  const int64_t i = (int64_t)blockIdx.x * SK_TILE + threadIdx.x;
-  const bool in = i < n;
-  const int64_t kl = !in ? 0 : kfix ? kfix : koff[i + 1];
-  const int64_t vl = in ? voff[i + 1] : 0;
-  int64_t ko = kl, vo = vl, tk, tv;
-  sk_block_scan2(ko, vo, tk, tv, ws);
-  ko += kfix ? (int64_t)blockIdx.x * SK_TILE * kfix : tsum[blockIdx.x];
-  vo += tsum[nT + 1 + blockIdx.x];
-  const int64_t wbase = __shfl(vo, 0, 64), wlen = __shfl(vo + vl, 63, 64) - wbase;  // past-n lanes: vl 0
-  const bool staged = wlen <= SK_WBUF;
-  uint8_t* vls = (uint8_t*)vst[wave];
-  bool isnull = true;
-  Val v0{0, nullptr, 0, true}, v1 = v0, v2 = v0, v3 = v0;  // the first four value columns
-  if (in) {
-    isnull = value_is_null(q, r, i);
-    if (!isnull) {
-      if (q.n_val > 0) v0 = row_value_val(q, r, i, 0);
-      if (q.n_val > 1) v1 = row_value_val(q, r, i, 1);
-      if (q.n_val > 2) v2 = row_value_val(q, r, i, 2);
-      if (q.n_val > 3) v3 = row_value_val(q, r, i, 3);
-    }
-  }
-  auto vget = [&](int c) {
-    return c == 0 ? v0 : c == 1 ? v1 : c == 2 ? v2 : c == 3 ? v3 : row_value_val(q, r, i, c);
-  };
-  auto no_elem = [](int, int, Val&) { return false; };  // (a scalar sink has no ARRAY column)
-  if (in && staged && !isnull) {
-    MemW vw{vls + (vo - wbase)};
-    put_value<false>(vw, q, vget, no_elem);
-  }
-  __syncthreads();
-  if (staged && wlen > 0) sk_wave_copy(vls, (int)wlen, vb + wbase);
-  if (in) {
-    if (kwords) {
-      put_key_words(q, r, i, (uint64_t*)(kb + ko));
-    } else {
-      MemW kw{kb + ko};
-      encode_key_row(kw, q, r, i);
-    }
-    sk_st(vnull + i, (uint8_t)(isnull ? 1 : 0));
-    if (!staged && !isnull) {
-      MemW vw{vb + vo};
-      put_value<false>(vw, q, vget, no_elem);
-    }
-    sk_st(koff + i + 1, ko + kl);
-    sk_st(voff + i + 1, vo + vl);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    koff[0] = 0;
-    voff[0] = 0;
-  }
-}
-
-// Pass 2 of a sink with an ARRAY column (a JSON value): k_sink_write's offsets, keys and outputs,
-// with another way for the values out.  A row with lists is long (64 rows pass SK_WBUF at 32 bytes
-// each), so the stage is the tile's: the tile's values are one contiguous range of tv bytes, and
-// the block goes over it in rounds of SK_ABUF bytes.  In a round every row that overlaps the
-// round's window encodes itself through WinW, which keeps the bytes inside the window (a row across
-// a window's edge encodes twice, each window taking its part), and the 256 threads copy the window
-// out in 16-byte stores.  A round's element loads come while only LDS is written; the next round's
-// wait once for the round's stores.  Rounds are uniform over the block (tv is), so the barriers
-// are too.  32 KB of LDS: four blocks per CU, the four waves per SIMD the register cap gives.
-__global__ KHIP_SINK_WRITE_LB void k_sink_write_arr(const SinkParams* __restrict__ qp, RowsDev r, int64_t n, int kfix,
-                                                    int kwords, int64_t nT, const int64_t* __restrict__ tsum,
-                                                    int64_t* __restrict__ koff, uint8_t* __restrict__ kb,
-                                                    int64_t* __restrict__ voff, uint8_t* __restrict__ vb,
-                                                    uint8_t* __restrict__ vnull) {
-  __shared__ int64_t ws[2][4];
-  __shared__ uint32_t ast[SK_ABUF / 4 + 4];
-  const SinkParams& q = *qp;
-  const int64_t i = (int64_t)blockIdx.x * SK_TILE + threadIdx.x;
-  const bool in = i < n;
-  const int64_t kl = !in ? 0 : kfix ? kfix : koff[i + 1];
-  const int64_t vl = in ? voff[i + 1] : 0;
-  int64_t ko = kl, vo = vl, tk, tv;
-  sk_block_scan2(ko, vo, tk, tv, ws);
-  ko += kfix ? (int64_t)blockIdx.x * SK_TILE * kfix : tsum[blockIdx.x];
-  const int64_t tbase = tsum[nT + 1 + blockIdx.x];  // the tile's first value byte; vo: the row's, within the tile
-  const bool isnull = in ? value_is_null(q, r, i) : true;
-  Val v0{0, nullptr, 0, true}, v1 = v0, v2 = v0, v3 = v0;  // the first four value columns (scalars)
-  if (!isnull) {
-    if (q.n_val > 0 && !q.varr[0]) v0 = row_value_val(q, r, i, 0);
-    if (q.n_val > 1 && !q.varr[1]) v1 = row_value_val(q, r, i, 1);
-    if (q.n_val > 2 && !q.varr[2]) v2 = row_value_val(q, r, i, 2);
-    if (q.n_val > 3 && !q.varr[3]) v3 = row_value_val(q, r, i, 3);
-  }
-  auto vget = [&](int c) {
-    return c == 0 ? v0 : c == 1 ? v1 : c == 2 ? v2 : c == 3 ? v3 : row_value_val(q, r, i, c);
-  };
-  const uint8_t* als = (const uint8_t*)ast;
-  for (int64_t lo = 0; lo < tv; lo += SK_ABUF) {
-    if (!isnull && vo < lo + SK_ABUF && vo + vl > lo) {
-      WinW vw{(sk_lds_u8*)ast, vo - lo};
-      put_value<true>(vw, q, vget, [&](int c, int e, Val& v) { return row_elem(q, r, i, c, e, v); });
-    }
-    __syncthreads();
-    sk_range_copy<256>(als, (int)(tv - lo < SK_ABUF ? tv - lo : SK_ABUF), vb + tbase + lo, threadIdx.x);
-    __syncthreads();
-  }
-  if (in) {
-    if (kwords) {
-      put_key_words(q, r, i, (uint64_t*)(kb + ko));
-    } else {
-      MemW kw{kb + ko};
-      encode_key_row(kw, q, r, i);
-    }
-    sk_st(vnull + i, (uint8_t)(isnull ? 1 : 0));
-    sk_st(koff + i + 1, ko + kl);
-    sk_st(voff + i + 1, tbase + vo + vl);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    koff[0] = 0;
-    voff[0] = 0;
-  }
-}
-
-// ------------------------------------------------------------------ the AVRO sink's kernels
+// ------------------------------------------------------------------ AVRO values of rows
 //
-// The value format AVRO has its own three kernels, with the structure of the three above (tiles,
-// offsets, keys, outputs and stages are theirs), so that the other formats' kernels stay as they
-// are.  What differs: the measure pass computes a value's length in closed form (no byte writer
-// runs), the encoder is put_avro_value, and a staged row goes to LDS through an LDS pointer (DS
-// stores, not FLAT ones).
+// put_avro_value's inputs from the rows, and a value's length in closed form: the measure pass of
+// an AVRO sink runs no byte writer.
 
 // the length of row i's list in ARRAY column c: row_elem's rule, the null bytes alone
 __device__ __forceinline__ int row_list_len(const SinkParams& q, const RowsDev& r, int64_t i, int c) {
@@ -974,162 +802,19 @@ __device__ __forceinline__ int64_t avro_value_len(const SinkParams& q, const Row
   return len;
 }
 
-struct LdsW {  // MemW into LDS
+struct LdsW {  // MemW into LDS: DS stores, not FLAT ones
   sk_lds_u8* p;
   __device__ __forceinline__ void put(uint8_t c) { *p++ = c; }
+  __device__ __forceinline__ static LdsW at(uint32_t* stage, int64_t off) { return LdsW{(sk_lds_u8*)stage + off}; }
 };
 
-template <bool ARR>
-__global__ __launch_bounds__(256) void k_sink_measure_avro(const SinkParams* __restrict__ qp, RowsDev r, int64_t n,
-                                                           int kfix, int64_t nT, int64_t* __restrict__ klen,
-                                                           int64_t* __restrict__ vlen, int64_t* __restrict__ tsum) {
-  __shared__ int64_t ws[2][4];
-  const SinkParams& q = *qp;
-  static_assert(SK_TR == 1, "one row per thread");
-  const int64_t i = (int64_t)blockIdx.x * SK_TILE + threadIdx.x;
-  int64_t sk = 0, sv = 0;
-  if (i < n) {
-    if (!kfix) {
-      CountW kw;
-      encode_key_row(kw, q, r, i);
-      klen[i + 1] = sk = kw.n;
-    }
-    if (!value_is_null(q, r, i)) sv = avro_value_len<ARR>(q, r, i);
-    vlen[i + 1] = sv;
-  }
-  sk_block_sum2(sk, sv, ws);
-  if (threadIdx.x == 0) {
-    tsum[1 + blockIdx.x] = sk;
-    tsum[nT + 2 + blockIdx.x] = sv;
-  }
-}
-
-// k_sink_write for AVRO values: the per-wave stage and the byte-wise way of a wave past SK_WBUF.
-__global__ KHIP_SINK_WRITE_LB void k_sink_write_avro(const SinkParams* __restrict__ qp, RowsDev r, int64_t n, int kfix,
-                                                     int kwords, int64_t nT, const int64_t* __restrict__ tsum,
-                                                     int64_t* __restrict__ koff, uint8_t* __restrict__ kb,
-                                                     int64_t* __restrict__ voff, uint8_t* __restrict__ vb,
-                                                     uint8_t* __restrict__ vnull, int32_t schema_id) {
-  __shared__ int64_t ws[2][4];
-  __shared__ uint32_t vst[4][SK_WBUF / 4 + 4];
-  const SinkParams& q = *qp;
-  const int wave = threadIdx.x >> 6;
-  const int64_t i = (int64_t)blockIdx.x * SK_TILE + threadIdx.x;
-  const bool in = i < n;
-  const int64_t kl = !in ? 0 : kfix ? kfix : koff[i + 1];
-  const int64_t vl = in ? voff[i + 1] : 0;
-  int64_t ko = kl, vo = vl, tk, tv;
-  sk_block_scan2(ko, vo, tk, tv, ws);
-  ko += kfix ? (int64_t)blockIdx.x * SK_TILE * kfix : tsum[blockIdx.x];
-  vo += tsum[nT + 1 + blockIdx.x];
-  const int64_t wbase = __shfl(vo, 0, 64), wlen = __shfl(vo + vl, 63, 64) - wbase;  // past-n lanes: vl 0
-  const bool staged = wlen <= SK_WBUF;
-  const bool isnull = in ? value_is_null(q, r, i) : true;
-  Val v0{0, nullptr, 0, true}, v1 = v0, v2 = v0, v3 = v0;  // the first four value columns
-  if (!isnull) {
-    if (q.n_val > 0) v0 = row_value_val(q, r, i, 0);
-    if (q.n_val > 1) v1 = row_value_val(q, r, i, 1);
-    if (q.n_val > 2) v2 = row_value_val(q, r, i, 2);
-    if (q.n_val > 3) v3 = row_value_val(q, r, i, 3);
-  }
-  auto vget = [&](int c) {
-    return c == 0 ? v0 : c == 1 ? v1 : c == 2 ? v2 : c == 3 ? v3 : row_value_val(q, r, i, c);
-  };
-  auto no_count = [](int) { return 0; };  // (a scalar sink has no ARRAY column)
-  auto no_elem = [](int, int, Val&) { return false; };
-  if (staged && !isnull) {
-    LdsW vw{(sk_lds_u8*)vst[wave] + (vo - wbase)};
-    put_avro_value<false>(vw, q, schema_id, vget, no_count, no_elem);
-  }
-  __syncthreads();
-  if (staged && wlen > 0) sk_wave_copy((const uint8_t*)vst[wave], (int)wlen, vb + wbase);
-  if (in) {
-    if (kwords) {
-      put_key_words(q, r, i, (uint64_t*)(kb + ko));
-    } else {
-      MemW kw{kb + ko};
-      encode_key_row(kw, q, r, i);
-    }
-    sk_st(vnull + i, (uint8_t)(isnull ? 1 : 0));
-    if (!staged && !isnull) {
-      MemW vw{vb + vo};
-      put_avro_value<false>(vw, q, schema_id, vget, no_count, no_elem);
-    }
-    sk_st(koff + i + 1, ko + kl);
-    sk_st(voff + i + 1, vo + vl);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    koff[0] = 0;
-    voff[0] = 0;
-  }
-}
-
-// k_sink_write_arr for AVRO values: the tile's stage in rounds of SK_ABUF bytes through WinW.
-__global__ KHIP_SINK_WRITE_LB void k_sink_write_arr_avro(const SinkParams* __restrict__ qp, RowsDev r, int64_t n,
-                                                         int kfix, int kwords, int64_t nT,
-                                                         const int64_t* __restrict__ tsum, int64_t* __restrict__ koff,
-                                                         uint8_t* __restrict__ kb, int64_t* __restrict__ voff,
-                                                         uint8_t* __restrict__ vb, uint8_t* __restrict__ vnull,
-                                                         int32_t schema_id) {
-  __shared__ int64_t ws[2][4];
-  __shared__ uint32_t ast[SK_ABUF / 4 + 4];
-  const SinkParams& q = *qp;
-  const int64_t i = (int64_t)blockIdx.x * SK_TILE + threadIdx.x;
-  const bool in = i < n;
-  const int64_t kl = !in ? 0 : kfix ? kfix : koff[i + 1];
-  const int64_t vl = in ? voff[i + 1] : 0;
-  int64_t ko = kl, vo = vl, tk, tv;
-  sk_block_scan2(ko, vo, tk, tv, ws);
-  ko += kfix ? (int64_t)blockIdx.x * SK_TILE * kfix : tsum[blockIdx.x];
-  const int64_t tbase = tsum[nT + 1 + blockIdx.x];  // the tile's first value byte; vo: the row's, within the tile
-  const bool isnull = in ? value_is_null(q, r, i) : true;
-  Val v0{0, nullptr, 0, true}, v1 = v0, v2 = v0, v3 = v0;  // the first four value columns (scalars)
-  if (!isnull) {
-    if (q.n_val > 0 && !q.varr[0]) v0 = row_value_val(q, r, i, 0);
-    if (q.n_val > 1 && !q.varr[1]) v1 = row_value_val(q, r, i, 1);
-    if (q.n_val > 2 && !q.varr[2]) v2 = row_value_val(q, r, i, 2);
-    if (q.n_val > 3 && !q.varr[3]) v3 = row_value_val(q, r, i, 3);
-  }
-  auto vget = [&](int c) {
-    return c == 0 ? v0 : c == 1 ? v1 : c == 2 ? v2 : c == 3 ? v3 : row_value_val(q, r, i, c);
-  };
-  const uint8_t* als = (const uint8_t*)ast;
-  for (int64_t lo = 0; lo < tv; lo += SK_ABUF) {
-    if (!isnull && vo < lo + SK_ABUF && vo + vl > lo) {
-      WinW vw{(sk_lds_u8*)ast, vo - lo};
-      put_avro_value<true>(vw, q, schema_id, vget, [&](int c) { return row_list_len(q, r, i, c); },
-                           [&](int c, int e, Val& v) { return row_elem(q, r, i, c, e, v); });
-    }
-    __syncthreads();
-    sk_range_copy<256>(als, (int)(tv - lo < SK_ABUF ? tv - lo : SK_ABUF), vb + tbase + lo, threadIdx.x);
-    __syncthreads();
-  }
-  if (in) {
-    if (kwords) {
-      put_key_words(q, r, i, (uint64_t*)(kb + ko));
-    } else {
-      MemW kw{kb + ko};
-      encode_key_row(kw, q, r, i);
-    }
-    sk_st(vnull + i, (uint8_t)(isnull ? 1 : 0));
-    sk_st(koff + i + 1, ko + kl);
-    sk_st(voff + i + 1, tbase + vo + vl);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    koff[0] = 0;
-    voff[0] = 0;
-  }
-}
-
-// ------------------------------------------------------------------ the PROTOBUF sink's kernels
+// ------------------------------------------------------------------ PROTOBUF values
 //
-// PROTOBUF / PROTOBUF_NOSR values (include/ksqldb_hip.h, "PROTOBUF values (sink)") run three kernels
-// of their own with the AVRO kernels' structure, so that every other format's kernels stay as they
-// are.  schema_id < 0 is the NOSR form (no framing); opt the `optional` representation.  A packed
-// list's length prefix depends on its payload, so the measure pass sizes the payload first; the
-// write pass sizes it again from the same elements.  A NULL element (null byte 2) has no protobuf
-// form: the measure pass raises *bad and the host answers KHIP_E_UNSUPPORTED before anything is
-// written.
+// PROTOBUF / PROTOBUF_NOSR values (include/ksqldb_hip.h, "PROTOBUF values (sink)").  schema_id < 0 is
+// the NOSR form (no framing); opt the `optional` representation.  A packed list's length prefix
+// depends on its payload, so the measure pass sizes the payload first; the write pass sizes it
+// again from the same elements.  A NULL element (null byte 2) has no protobuf form: the measure
+// pass raises *bad and the host answers KHIP_E_UNSUPPORTED before anything is written.
 
 // the varint of a sign-extended int32 / int64: 1..10 bytes
 __device__ __forceinline__ int pb_val_len(int type, const Val& v) {
@@ -1208,27 +893,139 @@ __device__ __forceinline__ void put_pb_value(W& w, const SinkParams& q, int32_t 
   }
 }
 
-template <bool ARR>
-__global__ __launch_bounds__(256) void k_sink_measure_pb(const SinkParams* __restrict__ qp, RowsDev r, int64_t n,
-                                                         int kfix, int64_t nT, int64_t* __restrict__ klen,
-                                                         int64_t* __restrict__ vlen, int64_t* __restrict__ tsum,
-                                                         int32_t schema_id, int opt, int32_t* __restrict__ bad) {
+// ------------------------------------------------------------------ the value encoders
+//
+// One policy per format family; the three kernels below are templates over it.  A policy says
+//   value_len<ARR>(m, q, r, i, &bad)  the bytes of row i's value (PROTOBUF: *bad on a NULL list element);
+//   put<ARR>(w, q, r, i, vval)        the value through the writer w, vval(c) being scalar column c (the
+//                                     list callbacks of the format are built here, from the rows);
+//   StageW                            the writer of k_sink_write's LDS stage;
+//   empty_ok                          a value that is not null may have no bytes;
+//   parent_shape                      TextEnc only: two places where the text kernels' statements stand
+//                                     in another order than the other formats', for no reason of the
+//                                     format: the measure kernel's row sits in a loop of one round, and
+//                                     k_sink_write tests the null value and loads the first columns
+//                                     inside `if (in)`.  They stay because the compiler makes other
+//                                     code without them (92 VGPRs for 95 and another descriptor in the
+//                                     measure kernel; sink_json measured 0.9 % slower without both).
+// The policy is a kernel argument of the write kernels, and its Measure one of the measure kernel:
+// the measure kernels of the text and AVRO formats take no argument, PROTOBUF's takes three, and
+// the kernels' argument bytes are to stay as they were, so Measure is a type of its own.
+
+// A kernel argument of no bytes.  An empty struct takes one byte of the kernel's arguments and moves
+// the hidden arguments behind it; a zero-length array member (a GNU extension that hipcc accepts)
+// makes sizeof 0, and the launch then copies nothing for it.  Should a compiler refuse the member or
+// give it a size, the static_assert below fails the build; nothing else depends on it.
+struct NoArgs {
+  int32_t none[0];
+  __device__ __forceinline__ void raise() const {}
+};
+
+struct TextEnc : NoArgs {  // JSON / DELIMITED / KAFKA: put_value; the length is a counting run of it
+  using Measure = NoArgs;
+  using StageW = MemW;
+  static constexpr bool empty_ok = false;
+  static constexpr bool parent_shape = true;
+  Measure measure(int32_t*) const { return {}; }
+  template <bool ARR, class W, class F>
+  __device__ __forceinline__ static void put(W& w, const SinkParams& q, const RowsDev& r, int64_t i, F&& vval) {
+    put_value<ARR>(w, q, vval, [&](int c, int e, Val& v) { return row_elem(q, r, i, c, e, v); });
+  }
+  template <bool ARR>
+  __device__ __forceinline__ static int64_t value_len(const Measure&, const SinkParams& q, const RowsDev& r, int64_t i,
+                                                      bool*) {
+    CountW w;
+    put<ARR>(w, q, r, i, [&](int c) { return row_value_val(q, r, i, c); });
+    return w.n;
+  }
+};
+static_assert(sizeof(TextEnc) == 0, "no kernel argument bytes");
+
+struct AvroEnc {
+  int32_t schema_id;
+  using Measure = NoArgs;
+  using StageW = LdsW;
+  static constexpr bool parent_shape = false;
+  static constexpr bool empty_ok = false;
+  Measure measure(int32_t*) const { return {}; }
+  template <bool ARR, class W, class F>
+  __device__ __forceinline__ void put(W& w, const SinkParams& q, const RowsDev& r, int64_t i, F&& vval) const {
+    put_avro_value<ARR>(w, q, schema_id, vval, [&](int c) { return row_list_len(q, r, i, c); },
+                        [&](int c, int e, Val& v) { return row_elem(q, r, i, c, e, v); });
+  }
+  template <bool ARR>
+  __device__ __forceinline__ static int64_t value_len(const Measure&, const SinkParams& q, const RowsDev& r, int64_t i,
+                                                      bool*) {
+    return avro_value_len<ARR>(q, r, i);
+  }
+};
+
+struct PbEnc {
+  int32_t schema_id;  // < 0: PROTOBUF_NOSR
+  int opt;
+  struct Measure {
+    int32_t schema_id;
+    int opt;
+    int32_t* bad;
+    __device__ __forceinline__ void raise() const { atomicOr(bad, 1); }
+  };
+  using StageW = LdsW;
+  static constexpr bool parent_shape = false;
+  static constexpr bool empty_ok = true;  // NOSR: no framing, every column absent
+  Measure measure(int32_t* bad) const { return {schema_id, opt, bad}; }
+  template <bool ARR, class W, class F>
+  __device__ __forceinline__ void put(W& w, const SinkParams& q, const RowsDev& r, int64_t i, F&& vval) const {
+    put_pb_value<ARR>(w, q, schema_id, opt, vval,
+                      [&](int c, int* cnt) {
+                        bool bad = false;
+                        return pb_list_payload(q, r, i, c, cnt, &bad);
+                      },
+                      [&](int c, int e, Val& v) { return row_elem(q, r, i, c, e, v); });
+  }
+  template <bool ARR>
+  __device__ __forceinline__ static int64_t value_len(const Measure& m, const SinkParams& q, const RowsDev& r, int64_t i,
+                                                      bool* bad) {
+    return pb_value_len<ARR>(q, r, i, m.schema_id, m.opt, bad);
+  }
+};
+
+// ------------------------------------------------------------------ the sink's kernels
+//
+// Three templates over the value encoder Enc.  ARR: the instantiation for sinks with an ARRAY
+// column (k_sink_measure<Enc, true> and k_sink_write_arr<Enc>); a scalar sink's kernels
+// (k_sink_measure<Enc, false>, k_sink_write<Enc>) carry none of it.
+
+// Pass 1: each row's key / value length at klen / vlen[i + 1] (keys skipped when every key is kfix
+// bytes), each tile's sums at tsum[1 + tile] (keys) and tsum[nT + 2 + tile] (values).
+template <class Enc, bool ARR>
+__global__ __launch_bounds__(256) void k_sink_measure(const SinkParams* __restrict__ qp, RowsDev r, int64_t n, int kfix,
+                                                      int64_t nT, int64_t* __restrict__ klen, int64_t* __restrict__ vlen,
+                                                      int64_t* __restrict__ tsum, typename Enc::Measure m) {
   __shared__ int64_t ws[2][4];
   const SinkParams& q = *qp;
-  static_assert(SK_TR == 1, "one row per thread");
   const int64_t i = (int64_t)blockIdx.x * SK_TILE + threadIdx.x;
   int64_t sk = 0, sv = 0;
-  bool b = false;
-  if (i < n) {
+  bool bad = false;
+  auto row = [&] {
     if (!kfix) {
       CountW kw;
       encode_key_row(kw, q, r, i);
-      klen[i + 1] = sk = kw.n;
+      klen[i + 1] = kw.n;
+      sk += kw.n;
     }
-    if (!value_is_null(q, r, i)) sv = pb_value_len<ARR>(q, r, i, schema_id, opt, &b);
+    if (!value_is_null(q, r, i)) sv = Enc::template value_len<ARR>(m, q, r, i, &bad);
     vlen[i + 1] = sv;
+  };
+  if constexpr (Enc::parent_shape) {
+#pragma unroll 1
+    for (int u = 0; u < 1; u++) {
+      if (i >= n) break;
+      row();
+    }
+  } else if (i < n) {
+    row();
   }
-  if (ARR && b) atomicOr(bad, 1);
+  if (ARR && bad) m.raise();
   sk_block_sum2(sk, sv, ws);
   if (threadIdx.x == 0) {
     tsum[1 + blockIdx.x] = sk;
@@ -1236,12 +1033,48 @@ __global__ __launch_bounds__(256) void k_sink_measure_pb(const SinkParams* __res
   }
 }
 
-// k_sink_write_avro for PROTOBUF values.
-__global__ KHIP_SINK_WRITE_LB void k_sink_write_pb(const SinkParams* __restrict__ qp, RowsDev r, int64_t n, int kfix,
-                                                   int kwords, int64_t nT, const int64_t* __restrict__ tsum,
-                                                   int64_t* __restrict__ koff, uint8_t* __restrict__ kb,
-                                                   int64_t* __restrict__ voff, uint8_t* __restrict__ vb,
-                                                   uint8_t* __restrict__ vnull, int32_t schema_id, int opt) {
+// Pass 2 (after sk_scan made tsum the tiles' offsets).  Its rules, for both write kernels:
+//   - every load of a row comes before its first global store (on gfx950 a load behind a store
+//     waits for the store): the lengths in the offsets prologue, the first value columns in
+//     SkFirst4, and the key's in put_key_words / encode_key_row before they store;
+//   - the barriers (sk_block_scan2's, the stages') are uniform over the block: past-n threads run
+//     them with lengths of 0;
+//   - each row's end offsets go over its own length slots (koff / voff[i + 1]: only this thread
+//     reads them, so no other tile's lengths are overwritten before they are read).
+// The offsets prologue and the outputs at the end stand in both kernels as plain statements, not
+// in helpers: moved into a function (a struct's constructor, a function with out-parameters, one
+// taking the last stores as a callable, one for the key alone) they are allocated other registers throughout, the
+// ARRAY writers of the text formats spill two more VGPRs, and those legs measured 2 to 4 % slower
+// (profiles/sink_templates/README.md).
+
+// The row's first four scalar value columns, loaded at once by load(); vval(c) for the encoders.
+template <bool ARR>
+struct SkFirst4 {
+  const SinkParams& q;
+  const RowsDev& r;
+  const int64_t i;
+  Val v0{0, nullptr, 0, true}, v1 = v0, v2 = v0, v3 = v0;
+  __device__ __forceinline__ SkFirst4(const SinkParams& q_, const RowsDev& r_, int64_t i_) : q(q_), r(r_), i(i_) {}
+  __device__ __forceinline__ void load() {
+    if (q.n_val > 0 && !(ARR && q.varr[0])) v0 = row_value_val(q, r, i, 0);
+    if (q.n_val > 1 && !(ARR && q.varr[1])) v1 = row_value_val(q, r, i, 1);
+    if (q.n_val > 2 && !(ARR && q.varr[2])) v2 = row_value_val(q, r, i, 2);
+    if (q.n_val > 3 && !(ARR && q.varr[3])) v3 = row_value_val(q, r, i, 3);
+  }
+  __device__ __forceinline__ Val operator()(int c) const {
+    return c == 0 ? v0 : c == 1 ? v1 : c == 2 ? v2 : c == 3 ? v3 : row_value_val(q, r, i, c);
+  }
+};
+
+// Pass 2 of a scalar sink.  A wave whose 64 values take at most SK_WBUF bytes (one contiguous
+// range of the output) encodes them into LDS at their places in that range and copies the range
+// out in 16-byte stores (sk_wave_copy); a longer wave writes each value at its offset byte by byte.
+template <class Enc>
+__global__ KHIP_SINK_WRITE_LB void k_sink_write(const SinkParams* __restrict__ qp, RowsDev r, int64_t n, int kfix,
+                                                int kwords, int64_t nT, const int64_t* __restrict__ tsum,
+                                                int64_t* __restrict__ koff, uint8_t* __restrict__ kb,
+                                                int64_t* __restrict__ voff, uint8_t* __restrict__ vb,
+                                                uint8_t* __restrict__ vnull, Enc enc) {
   __shared__ int64_t ws[2][4];
   __shared__ uint32_t vst[4][SK_WBUF / 4 + 4];
   const SinkParams& q = *qp;
@@ -1256,36 +1089,34 @@ __global__ KHIP_SINK_WRITE_LB void k_sink_write_pb(const SinkParams* __restrict_
   vo += tsum[nT + 1 + blockIdx.x];
   const int64_t wbase = __shfl(vo, 0, 64), wlen = __shfl(vo + vl, 63, 64) - wbase;  // past-n lanes: vl 0
   const bool staged = wlen <= SK_WBUF;
-  const bool isnull = in ? value_is_null(q, r, i) : true;
-  Val v0{0, nullptr, 0, true}, v1 = v0, v2 = v0, v3 = v0;  // the first four value columns
-  if (!isnull) {
-    if (q.n_val > 0) v0 = row_value_val(q, r, i, 0);
-    if (q.n_val > 1) v1 = row_value_val(q, r, i, 1);
-    if (q.n_val > 2) v2 = row_value_val(q, r, i, 2);
-    if (q.n_val > 3) v3 = row_value_val(q, r, i, 3);
+  SkFirst4<false> vval(q, r, i);
+  bool isnull = true;
+  if constexpr (Enc::parent_shape) {
+    if (in) {
+      isnull = value_is_null(q, r, i);
+      if (!isnull) vval.load();
+    }
+  } else {
+    isnull = in ? value_is_null(q, r, i) : true;
+    if (!isnull) vval.load();
   }
-  auto vget = [&](int c) {
-    return c == 0 ? v0 : c == 1 ? v1 : c == 2 ? v2 : c == 3 ? v3 : row_value_val(q, r, i, c);
-  };
-  auto no_payload = [](int, int*) { return (int64_t)0; };  // (a scalar sink has no ARRAY column)
-  auto no_elem = [](int, int, Val&) { return false; };
-  if (staged && !isnull && vl > 0) {
-    LdsW vw{(sk_lds_u8*)vst[wave] + (vo - wbase)};
-    put_pb_value<false>(vw, q, schema_id, opt, vget, no_payload, no_elem);
+  if ((!Enc::parent_shape || in) && staged && !isnull && (!Enc::empty_ok || vl > 0)) {
+    auto vw = Enc::StageW::at(vst[wave], vo - wbase);
+    enc.template put<false>(vw, q, r, i, vval);
   }
   __syncthreads();
   if (staged && wlen > 0) sk_wave_copy((const uint8_t*)vst[wave], (int)wlen, vb + wbase);
   if (in) {
-    if (kwords) {
+    if (kwords) {  // the key as kfix / 8 words
       put_key_words(q, r, i, (uint64_t*)(kb + ko));
     } else {
       MemW kw{kb + ko};
       encode_key_row(kw, q, r, i);
     }
     sk_st(vnull + i, (uint8_t)(isnull ? 1 : 0));
-    if (!staged && !isnull && vl > 0) {
+    if (!staged && !isnull && (!Enc::empty_ok || vl > 0)) {
       MemW vw{vb + vo};
-      put_pb_value<false>(vw, q, schema_id, opt, vget, no_payload, no_elem);
+      enc.template put<false>(vw, q, r, i, vval);
     }
     sk_st(koff + i + 1, ko + kl);
     sk_st(voff + i + 1, vo + vl);
@@ -1296,13 +1127,21 @@ __global__ KHIP_SINK_WRITE_LB void k_sink_write_pb(const SinkParams* __restrict_
   }
 }
 
-// k_sink_write_arr_avro for PROTOBUF values.
-__global__ KHIP_SINK_WRITE_LB void k_sink_write_arr_pb(const SinkParams* __restrict__ qp, RowsDev r, int64_t n,
-                                                       int kfix, int kwords, int64_t nT,
-                                                       const int64_t* __restrict__ tsum, int64_t* __restrict__ koff,
-                                                       uint8_t* __restrict__ kb, int64_t* __restrict__ voff,
-                                                       uint8_t* __restrict__ vb, uint8_t* __restrict__ vnull,
-                                                       int32_t schema_id, int opt) {
+// Pass 2 of a sink with an ARRAY column: k_sink_write's offsets, keys and outputs, with another way
+// for the values out.  A row with lists is long (64 rows pass SK_WBUF at 32 bytes each), so the
+// stage is the tile's: the tile's values are one contiguous range of tv bytes, and the block goes
+// over it in rounds of SK_ABUF bytes.  In a round every row that overlaps the round's window
+// encodes itself through WinW, which keeps the bytes inside the window (a row across a window's
+// edge encodes twice, each window taking its part), and the 256 threads copy the window out in
+// 16-byte stores.  A round's element loads come while only LDS is written; the next round's wait
+// once for the round's stores.  Rounds are uniform over the block (tv is), so the barriers are
+// too.  32 KB of LDS: four blocks per CU, the four waves per SIMD the register cap gives.
+template <class Enc>
+__global__ KHIP_SINK_WRITE_LB void k_sink_write_arr(const SinkParams* __restrict__ qp, RowsDev r, int64_t n, int kfix,
+                                                    int kwords, int64_t nT, const int64_t* __restrict__ tsum,
+                                                    int64_t* __restrict__ koff, uint8_t* __restrict__ kb,
+                                                    int64_t* __restrict__ voff, uint8_t* __restrict__ vb,
+                                                    uint8_t* __restrict__ vnull, Enc enc) {
   __shared__ int64_t ws[2][4];
   __shared__ uint32_t ast[SK_ABUF / 4 + 4];
   const SinkParams& q = *qp;
@@ -1315,33 +1154,20 @@ __global__ KHIP_SINK_WRITE_LB void k_sink_write_arr_pb(const SinkParams* __restr
   ko += kfix ? (int64_t)blockIdx.x * SK_TILE * kfix : tsum[blockIdx.x];
   const int64_t tbase = tsum[nT + 1 + blockIdx.x];  // the tile's first value byte; vo: the row's, within the tile
   const bool isnull = in ? value_is_null(q, r, i) : true;
-  Val v0{0, nullptr, 0, true}, v1 = v0, v2 = v0, v3 = v0;  // the first four value columns (scalars)
-  if (!isnull) {
-    if (q.n_val > 0 && !q.varr[0]) v0 = row_value_val(q, r, i, 0);
-    if (q.n_val > 1 && !q.varr[1]) v1 = row_value_val(q, r, i, 1);
-    if (q.n_val > 2 && !q.varr[2]) v2 = row_value_val(q, r, i, 2);
-    if (q.n_val > 3 && !q.varr[3]) v3 = row_value_val(q, r, i, 3);
-  }
-  auto vget = [&](int c) {
-    return c == 0 ? v0 : c == 1 ? v1 : c == 2 ? v2 : c == 3 ? v3 : row_value_val(q, r, i, c);
-  };
+  SkFirst4<true> vval(q, r, i);
+  if (!isnull) vval.load();
   const uint8_t* als = (const uint8_t*)ast;
   for (int64_t lo = 0; lo < tv; lo += SK_ABUF) {
     if (!isnull && vo < lo + SK_ABUF && vo + vl > lo) {
       WinW vw{(sk_lds_u8*)ast, vo - lo};
-      put_pb_value<true>(vw, q, schema_id, opt, vget,
-                         [&](int c, int* cnt) {
-                           bool bad = false;
-                           return pb_list_payload(q, r, i, c, cnt, &bad);
-                         },
-                         [&](int c, int e, Val& v) { return row_elem(q, r, i, c, e, v); });
+      enc.template put<true>(vw, q, r, i, vval);
     }
     __syncthreads();
     sk_range_copy<256>(als, (int)(tv - lo < SK_ABUF ? tv - lo : SK_ABUF), vb + tbase + lo, threadIdx.x);
     __syncthreads();
   }
   if (in) {
-    if (kwords) {
+    if (kwords) {  // the key as kfix / 8 words
       put_key_words(q, r, i, (uint64_t*)(kb + ko));
     } else {
       MemW kw{kb + ko};
@@ -1486,9 +1312,9 @@ struct khip_sink {
   khip_sink_desc desc{};
   SinkParams q{};
   int device = 0;
-  bool has_arr = false;        // some value column is an ARRAY: the k_sink_*<true> / _arr kernels
-  int32_t avro_id = -1;        // AVRO / PROTOBUF values: the schema id of the records' header; -1 = not set yet
-  bool pb = false;             // PROTOBUF / PROTOBUF_NOSR values: the k_sink_*_pb kernels
+  bool has_arr = false;        // some value column is an ARRAY: k_sink_measure<Enc, true> / k_sink_write_arr<Enc>
+  int32_t schema_id = -1;      // AVRO / PROTOBUF values: the schema id of the records' header; -1 = not set yet
+  bool pb = false;             // PROTOBUF / PROTOBUF_NOSR values: PbEnc
   int pb_opt = 0;              // KHIP_PROTO_OPTIONAL: scalars have presence
   DevBuf pb_bad;               // the measure pass's flag: some list holds a NULL element
   int32_t src_len[SK_MAX] = {};  // per rows column: its ARRAY length L, 0 = scalar
@@ -1531,6 +1357,221 @@ khip_status sk_scan(khip_sink* s, DevBuf& ws, int64_t* off, int64_t n, int64_t* 
 
 bool sk_type_ok(int t, bool str) {
   return t == KHIP_TYPE_INT32 || t == KHIP_TYPE_INT64 || t == KHIP_TYPE_DOUBLE || (str && t == KHIP_TYPE_STRING);
+}
+
+khip_status sk_set_schema_id(khip_sink* s, int32_t schema_id, std::initializer_list<int> formats, const char* whose) {
+  clear_error();
+  if (!s) return fail(KHIP_E_INVALID, "null argument");
+  if (std::find(formats.begin(), formats.end(), s->q.value_format) == formats.end()) return fail(KHIP_E_INVALID, whose);
+  if (schema_id < 0) return fail(KHIP_E_INVALID, "negative schema id");
+  s->schema_id = schema_id;
+  return KHIP_OK;
+}
+
+// f(enc) with the sink's value encoder: the one place that picks it
+template <class F>
+void sk_with_enc(const khip_sink* s, F&& f) {
+  if (s->pb) f(PbEnc{s->q.value_format == KHIP_FMT_PROTOBUF ? s->schema_id : -1, s->pb_opt});  // NOSR: no framing
+  else if (s->q.value_format == KHIP_FMT_AVRO) f(AvroEnc{s->schema_id});
+  else f(TextEnc{});
+}
+
+// ---- khip_sink_encode's stages, in their order; SinkCall is what one hands to the next
+
+struct SinkCall {
+  int64_t n = 0, nT = 0;  // rows, tiles
+  bool str_key = false, dev_out = false;
+  int ncol = 0;       // rows columns up to the last one read
+  int ctype[SK_MAX];
+  bool used[SK_MAX];  // columns some value column reads: only those are staged or passed on
+  RowsDev r{};
+  int kfix = 0;       // every key this many bytes: a KAFKA INT32 / BIGINT key and its window suffix
+  int64_t *koff = nullptr, *voff = nullptr;  // the offsets: the device outputs, else the handle's buffers
+  int64_t ktot = 0, vtot = 0;
+  uint8_t *kb = nullptr, *vb = nullptr, *vn = nullptr;  // likewise the bytes and the null flags
+};
+
+khip_status enc_check_args(khip_sink* s, const khip_sink_rows* rows, khip_sink_out* out, SinkCall& c) {
+  const SinkParams& q = s->q;
+  if (q.value_format == KHIP_FMT_AVRO && s->schema_id < 0)
+    return fail(KHIP_E_STATE, "AVRO values need khip_sink_set_avro_schema_id first");
+  if (q.value_format == KHIP_FMT_PROTOBUF && s->schema_id < 0)
+    return fail(KHIP_E_STATE, "PROTOBUF values need khip_sink_set_schema_id first");
+  const int64_t n = c.n = rows->n_rows;
+  if (n < 0 || !out->key_offsets || !out->value_offsets || !out->value_null) return fail(KHIP_E_INVALID, "rows / outputs");
+  const bool windowed = q.window_kind != KHIP_WINDOW_NONE;
+  if (n && windowed && !rows->window_start) return fail(KHIP_E_INVALID, "a windowed key needs window_start");
+  if (n && q.window_kind == KHIP_WINDOW_SESSION && !rows->window_end) return fail(KHIP_E_INVALID, "a session key needs window_end");
+  c.str_key = rows->key_serialized || q.ktype[0] == KHIP_TYPE_STRING;
+  if (!rows->key_serialized && (q.n_key != 1 || q.ktype[0] == KHIP_TYPE_DOUBLE))
+    return fail(KHIP_E_INVALID, "row keys: one INT32/INT64/STRING key column, or serialized keys");
+  if (n && (c.str_key ? !(rows->key_offsets && rows->key_bytes) : !rows->key_i64))
+    return fail(KHIP_E_INVALID, "row key arrays");
+  for (int k = 0; k < SK_MAX; k++) {
+    c.ctype[k] = KHIP_TYPE_INT64;
+    c.used[k] = false;
+  }
+  for (int k = 0; k < q.n_val; k++) {
+    const int src = q.vsrc[k];
+    if (src == KHIP_SINK_SRC_WS && n && !rows->window_start) return fail(KHIP_E_INVALID, "WINDOWSTART source");
+    if (src == KHIP_SINK_SRC_WE && n && !rows->window_end) return fail(KHIP_E_INVALID, "WINDOWEND source");
+    if (src >= 0) {
+      if (n && (!rows->col_data || !rows->col_data[src])) return fail(KHIP_E_INVALID, "value source column");
+      if (n && q.varr[k] && (!rows->col_null || !rows->col_null[src]))
+        return fail(KHIP_E_INVALID, "an ARRAY value column needs col_null (the list's length lives in its null bytes)");
+      c.ncol = std::max(c.ncol, src + 1);
+      c.ctype[src] = q.vtype[k];
+      c.used[src] = true;
+    }
+  }
+  return KHIP_OK;
+}
+
+// c.r: the rows as the kernels read them; host rows are copied to the handle's staging buffers
+khip_status enc_stage_rows(khip_sink* s, const khip_sink_rows* rows, SinkCall& c) {
+  const int64_t n = c.n;
+  RowsDev& r = c.r;
+  r.key_serialized = rows->key_serialized;
+  r.key_i64 = rows->key_i64;
+  r.key_off = rows->key_offsets;
+  r.key_bytes = rows->key_bytes;
+  r.ws = rows->window_start;
+  r.we = rows->window_end;
+  r.tomb = rows->tombstone;
+  for (int k = 0; k < c.ncol; k++) {
+    r.col[k] = c.used[k] && rows->col_data ? rows->col_data[k] : nullptr;
+    r.cnull[k] = c.used[k] && rows->col_null ? rows->col_null[k] : nullptr;
+  }
+  if (rows->mem == KHIP_MEM_HOST && n) {
+    const void* p;
+    if (c.str_key) {
+      KHIP_TRY(sk_stage(s, s->st_koff, rows->key_offsets, (size_t)(n + 1) * 8, &p));
+      r.key_off = (const int64_t*)p;
+      KHIP_TRY(sk_stage(s, s->st_kbytes, rows->key_bytes, (size_t)rows->key_offsets[n], &p));
+      r.key_bytes = (const uint8_t*)p;
+    } else {
+      KHIP_TRY(sk_stage(s, s->st_key, rows->key_i64, (size_t)n * 8, &p));
+      r.key_i64 = (const int64_t*)p;
+    }
+    KHIP_TRY(sk_stage(s, s->st_ws, rows->window_start, (size_t)n * 8, &p));
+    r.ws = (const int64_t*)p;
+    KHIP_TRY(sk_stage(s, s->st_we, rows->window_end, (size_t)n * 8, &p));
+    r.we = (const int64_t*)p;
+    KHIP_TRY(sk_stage(s, s->st_tomb, rows->tombstone, (size_t)n, &p));
+    r.tomb = (const uint8_t*)p;
+    for (int k = 0; k < c.ncol; k++) {
+      if (!c.used[k] || !rows->col_data[k]) continue;
+      const size_t ne = (size_t)n * (size_t)std::max(s->src_len[k], 1);  // ARRAY: n x L elements and null bytes
+      KHIP_TRY(sk_stage(s, s->st_col[k], rows->col_data[k], ne * (c.ctype[k] == KHIP_TYPE_INT32 ? 4 : 8), &p));
+      r.col[k] = p;
+      KHIP_TRY(sk_stage(s, s->st_null[k], rows->col_null ? rows->col_null[k] : nullptr, ne, &p));
+      r.cnull[k] = (const uint8_t*)p;
+    }
+  } else if (rows->mem != KHIP_MEM_HOST && rows->mem != KHIP_MEM_DEVICE) {
+    return fail(KHIP_E_INVALID, "rows mem");
+  }
+  return KHIP_OK;
+}
+
+// Pass 1 and the scans: the lengths at c.koff / c.voff become offsets, c.ktot / c.vtot the totals.
+khip_status enc_measure(khip_sink* s, const khip_sink_rows* rows, khip_sink_out* out, SinkCall& c) {
+  const SinkParams& q = s->q;
+  const int64_t n = c.n;
+  if (out->mem != KHIP_MEM_HOST && out->mem != KHIP_MEM_DEVICE) return fail(KHIP_E_INVALID, "output mem");
+  c.dev_out = out->mem == KHIP_MEM_DEVICE;
+  if (c.dev_out) {
+    c.koff = out->key_offsets;
+    c.voff = out->value_offsets;
+  } else {
+    KHIP_TRY(s->koff.ensure((size_t)(n + 1) * 8));
+    KHIP_TRY(s->voff.ensure((size_t)(n + 1) * 8));
+    c.koff = s->koff.as<int64_t>();
+    c.voff = s->voff.as<int64_t>();
+  }
+  c.nT = ceil_div(n, SK_TILE);
+  if (!rows->key_serialized && q.key_format == KHIP_FMT_KAFKA && q.ktype[0] != KHIP_TYPE_STRING)
+    c.kfix = (q.ktype[0] == KHIP_TYPE_INT64 ? 8 : 4) +
+             (q.window_kind == KHIP_WINDOW_SESSION ? 16 : q.window_kind != KHIP_WINDOW_NONE ? 8 : 0);
+  if (!n) {
+    const int64_t z = 0;
+    if (c.dev_out) {
+      KHIP_TRY_HIP(hipMemcpyAsync(c.koff, &z, 8, hipMemcpyHostToDevice, s->stream));
+      KHIP_TRY_HIP(hipMemcpyAsync(c.voff, &z, 8, hipMemcpyHostToDevice, s->stream));
+      KHIP_TRY_HIP(hipStreamSynchronize(s->stream));
+    }
+    return KHIP_OK;
+  }
+  KHIP_TRY(s->tsum.ensure((size_t)(2 * (c.nT + 1)) * 8));
+  int64_t* ts = s->tsum.as<int64_t>();
+  const bool may_be_bad = s->pb && s->has_arr;  // a NULL list element: PbEnc raises the flag
+  if (s->pb) KHIP_TRY(s->pb_bad.ensure(8));
+  if (may_be_bad) KHIP_TRY_HIP(hipMemsetAsync(s->pb_bad.p, 0, 8, s->stream));
+  sk_with_enc(s, [&](auto enc) {
+    using Enc = decltype(enc);
+    hipLaunchKernelGGL((s->has_arr ? k_sink_measure<Enc, true> : k_sink_measure<Enc, false>), dim3((unsigned)c.nT),
+                       dim3(256), 0, s->stream, s->dq.as<SinkParams>(), c.r, n, c.kfix, c.nT, c.koff, c.voff, ts,
+                       enc.measure(s->pb_bad.as<int32_t>()));
+  });
+  KHIP_TRY_HIP(hipGetLastError());
+  int64_t tk = 0, tv = 0;
+  int32_t bad = 0;
+  if (may_be_bad) KHIP_TRY_HIP(hipMemcpyAsync(&bad, s->pb_bad.p, 4, hipMemcpyDeviceToHost, s->stream));
+  if (!c.kfix) KHIP_TRY(sk_scan(s, s->bsum, ts, c.nT, &tk, false));
+  KHIP_TRY(sk_scan(s, s->bsum2, ts + c.nT + 1, c.nT, &tv, true));
+  if (bad)
+    return fail(KHIP_E_UNSUPPORTED, "a NULL array element has no PROTOBUF form (the query stays with the reference)");
+  c.ktot = c.kfix ? (int64_t)c.kfix * n : tk;
+  c.vtot = tv;
+  return KHIP_OK;
+}
+
+// the totals to the caller; c.kb / c.vb / c.vn: where pass 2 writes
+khip_status enc_out_buffers(khip_sink* s, khip_sink_out* out, SinkCall& c) {
+  out->key_len = c.ktot;
+  out->value_len = c.vtot;
+  if (c.ktot > out->key_capacity || c.vtot > out->value_capacity) return fail(KHIP_E_BUFFER, "sink output capacity too small");
+  if (c.n && (c.ktot && !out->key_bytes)) return fail(KHIP_E_INVALID, "key_bytes");
+  if (c.n && (c.vtot && !out->value_bytes)) return fail(KHIP_E_INVALID, "value_bytes");
+  c.kb = out->key_bytes;
+  c.vb = out->value_bytes;
+  c.vn = out->value_null;
+  if (!c.dev_out) {
+    KHIP_TRY(s->kbytes.ensure((size_t)std::max<int64_t>(c.ktot, 8)));
+    KHIP_TRY(s->vbytes.ensure((size_t)std::max<int64_t>(c.vtot, 8)));
+    KHIP_TRY(s->vnull.ensure((size_t)std::max<int64_t>(c.n, 8)));
+    c.kb = s->kbytes.as<uint8_t>();
+    c.vb = s->vbytes.as<uint8_t>();
+    c.vn = s->vnull.as<uint8_t>();
+  }
+  return KHIP_OK;
+}
+
+// Pass 2
+khip_status enc_write(khip_sink* s, const SinkCall& c) {
+  if (!c.n) return KHIP_OK;
+  const int kwords = c.kfix && s->q.ktype[0] == KHIP_TYPE_INT64 && ((uintptr_t)c.kb & 7) == 0 ? c.kfix / 8 : 0;
+  sk_with_enc(s, [&](auto enc) {
+    using Enc = decltype(enc);
+    hipLaunchKernelGGL((s->has_arr ? k_sink_write_arr<Enc> : k_sink_write<Enc>), dim3((unsigned)c.nT), dim3(256), 0,
+                       s->stream, s->dq.as<SinkParams>(), c.r, c.n, c.kfix, kwords, c.nT, s->tsum.as<int64_t>(), c.koff,
+                       c.kb, c.voff, c.vb, c.vn, enc);
+  });
+  KHIP_TRY_HIP(hipGetLastError());
+  return KHIP_OK;
+}
+
+// host outputs: the handle's buffers to the caller's; the call ends synchronised either way
+khip_status enc_copy_out(khip_sink* s, khip_sink_out* out, const SinkCall& c) {
+  if (!c.dev_out) {
+    const int64_t n = c.n;
+    KHIP_TRY_HIP(hipMemcpyAsync(out->key_offsets, c.koff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s->stream));
+    KHIP_TRY_HIP(hipMemcpyAsync(out->value_offsets, c.voff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s->stream));
+    if (n) KHIP_TRY_HIP(hipMemcpyAsync(out->value_null, c.vn, (size_t)n, hipMemcpyDeviceToHost, s->stream));
+    if (c.ktot) KHIP_TRY_HIP(hipMemcpyAsync(out->key_bytes, c.kb, (size_t)c.ktot, hipMemcpyDeviceToHost, s->stream));
+    if (c.vtot) KHIP_TRY_HIP(hipMemcpyAsync(out->value_bytes, c.vb, (size_t)c.vtot, hipMemcpyDeviceToHost, s->stream));
+  }
+  KHIP_TRY_HIP(hipStreamSynchronize(s->stream));
+  return KHIP_OK;
 }
 
 }  // namespace
@@ -1659,22 +1700,12 @@ khip_status khip_sink_create(const khip_sink_desc* d, khip_sink** out) {
 }
 
 khip_status khip_sink_set_avro_schema_id(khip_sink* s, int32_t schema_id) {
-  clear_error();
-  if (!s) return fail(KHIP_E_INVALID, "null argument");
-  if (s->q.value_format != KHIP_FMT_AVRO) return fail(KHIP_E_INVALID, "a schema id belongs to the AVRO value format");
-  if (schema_id < 0) return fail(KHIP_E_INVALID, "negative schema id");
-  s->avro_id = schema_id;
-  return KHIP_OK;
+  return sk_set_schema_id(s, schema_id, {KHIP_FMT_AVRO}, "a schema id belongs to the AVRO value format");
 }
 
 khip_status khip_sink_set_schema_id(khip_sink* s, int32_t schema_id) {
-  clear_error();
-  if (!s) return fail(KHIP_E_INVALID, "null argument");
-  if (s->q.value_format != KHIP_FMT_AVRO && s->q.value_format != KHIP_FMT_PROTOBUF)
-    return fail(KHIP_E_INVALID, "a schema id belongs to the AVRO and PROTOBUF value formats");
-  if (schema_id < 0) return fail(KHIP_E_INVALID, "negative schema id");
-  s->avro_id = schema_id;
-  return KHIP_OK;
+  return sk_set_schema_id(s, schema_id, {KHIP_FMT_AVRO, KHIP_FMT_PROTOBUF},
+                          "a schema id belongs to the AVRO and PROTOBUF value formats");
 }
 
 khip_status khip_sink_key(khip_sink* s, const khip_batch* in, const khip_key_col* cols, khip_batch* out) {
@@ -1753,171 +1784,14 @@ khip_status khip_sink_key(khip_sink* s, const khip_batch* in, const khip_key_col
 khip_status khip_sink_encode(khip_sink* s, const khip_sink_rows* rows, khip_sink_out* out) {
   clear_error();
   if (!s || !rows || !out) return fail(KHIP_E_INVALID, "null argument");
-  const SinkParams& q = s->q;
-  const bool avro = q.value_format == KHIP_FMT_AVRO;
-  if (avro && s->avro_id < 0) return fail(KHIP_E_STATE, "AVRO values need khip_sink_set_avro_schema_id first");
-  if (q.value_format == KHIP_FMT_PROTOBUF && s->avro_id < 0)
-    return fail(KHIP_E_STATE, "PROTOBUF values need khip_sink_set_schema_id first");
-  const int32_t pb_id = q.value_format == KHIP_FMT_PROTOBUF ? s->avro_id : -1;  // NOSR: no framing
-  const int64_t n = rows->n_rows;
-  if (n < 0 || !out->key_offsets || !out->value_offsets || !out->value_null) return fail(KHIP_E_INVALID, "rows / outputs");
-  const bool windowed = q.window_kind != KHIP_WINDOW_NONE;
-  if (n && windowed && !rows->window_start) return fail(KHIP_E_INVALID, "a windowed key needs window_start");
-  if (n && q.window_kind == KHIP_WINDOW_SESSION && !rows->window_end) return fail(KHIP_E_INVALID, "a session key needs window_end");
-  const bool str_key = rows->key_serialized || q.ktype[0] == KHIP_TYPE_STRING;
-  if (!rows->key_serialized && (q.n_key != 1 || q.ktype[0] == KHIP_TYPE_DOUBLE))
-    return fail(KHIP_E_INVALID, "row keys: one INT32/INT64/STRING key column, or serialized keys");
-  if (n && (str_key ? !(rows->key_offsets && rows->key_bytes) : !rows->key_i64))
-    return fail(KHIP_E_INVALID, "row key arrays");
-  int ncol = 0;
-  int ctype[SK_MAX];
-  bool used[SK_MAX];  // columns some value column reads: only those are staged or passed on
-  for (int c = 0; c < SK_MAX; c++) {
-    ctype[c] = KHIP_TYPE_INT64;
-    used[c] = false;
-  }
-  for (int c = 0; c < q.n_val; c++) {
-    const int src = q.vsrc[c];
-    if (src == KHIP_SINK_SRC_WS && n && !rows->window_start) return fail(KHIP_E_INVALID, "WINDOWSTART source");
-    if (src == KHIP_SINK_SRC_WE && n && !rows->window_end) return fail(KHIP_E_INVALID, "WINDOWEND source");
-    if (src >= 0) {
-      if (n && (!rows->col_data || !rows->col_data[src])) return fail(KHIP_E_INVALID, "value source column");
-      if (n && q.varr[c] && (!rows->col_null || !rows->col_null[src]))
-        return fail(KHIP_E_INVALID, "an ARRAY value column needs col_null (the list's length lives in its null bytes)");
-      ncol = std::max(ncol, src + 1);
-      ctype[src] = q.vtype[c];
-      used[src] = true;
-    }
-  }
+  SinkCall c;
+  KHIP_TRY(enc_check_args(s, rows, out, c));
   DeviceGuard g(s->device);
-  RowsDev r{};
-  r.key_serialized = rows->key_serialized;
-  r.key_i64 = rows->key_i64;
-  r.key_off = rows->key_offsets;
-  r.key_bytes = rows->key_bytes;
-  r.ws = rows->window_start;
-  r.we = rows->window_end;
-  r.tomb = rows->tombstone;
-  for (int c = 0; c < ncol; c++) {
-    r.col[c] = used[c] && rows->col_data ? rows->col_data[c] : nullptr;
-    r.cnull[c] = used[c] && rows->col_null ? rows->col_null[c] : nullptr;
-  }
-  if (rows->mem == KHIP_MEM_HOST && n) {
-    const void* p;
-    if (str_key) {
-      KHIP_TRY(sk_stage(s, s->st_koff, rows->key_offsets, (size_t)(n + 1) * 8, &p));
-      r.key_off = (const int64_t*)p;
-      KHIP_TRY(sk_stage(s, s->st_kbytes, rows->key_bytes, (size_t)rows->key_offsets[n], &p));
-      r.key_bytes = (const uint8_t*)p;
-    } else {
-      KHIP_TRY(sk_stage(s, s->st_key, rows->key_i64, (size_t)n * 8, &p));
-      r.key_i64 = (const int64_t*)p;
-    }
-    KHIP_TRY(sk_stage(s, s->st_ws, rows->window_start, (size_t)n * 8, &p));
-    r.ws = (const int64_t*)p;
-    KHIP_TRY(sk_stage(s, s->st_we, rows->window_end, (size_t)n * 8, &p));
-    r.we = (const int64_t*)p;
-    KHIP_TRY(sk_stage(s, s->st_tomb, rows->tombstone, (size_t)n, &p));
-    r.tomb = (const uint8_t*)p;
-    for (int c = 0; c < ncol; c++) {
-      if (!used[c] || !rows->col_data[c]) continue;
-      const size_t ne = (size_t)n * (size_t)std::max(s->src_len[c], 1);  // ARRAY: n x L elements and null bytes
-      KHIP_TRY(sk_stage(s, s->st_col[c], rows->col_data[c], ne * (ctype[c] == KHIP_TYPE_INT32 ? 4 : 8), &p));
-      r.col[c] = p;
-      KHIP_TRY(sk_stage(s, s->st_null[c], rows->col_null ? rows->col_null[c] : nullptr, ne, &p));
-      r.cnull[c] = (const uint8_t*)p;
-    }
-  } else if (rows->mem != KHIP_MEM_HOST && rows->mem != KHIP_MEM_DEVICE) {
-    return fail(KHIP_E_INVALID, "rows mem");
-  }
-  if (out->mem != KHIP_MEM_HOST && out->mem != KHIP_MEM_DEVICE) return fail(KHIP_E_INVALID, "output mem");
-  const bool dev_out = out->mem == KHIP_MEM_DEVICE;
-  // offsets: straight into device outputs, else into the handle's buffers
-  int64_t *koff = dev_out ? out->key_offsets : nullptr, *voff = dev_out ? out->value_offsets : nullptr;
-  if (!dev_out) {
-    KHIP_TRY(s->koff.ensure((size_t)(n + 1) * 8));
-    KHIP_TRY(s->voff.ensure((size_t)(n + 1) * 8));
-    koff = s->koff.as<int64_t>();
-    voff = s->voff.as<int64_t>();
-  }
-  int64_t ktot = 0, vtot = 0;
-  const int64_t nT = ceil_div(n, SK_TILE);
-  // every key the same width: a KAFKA INT32 / BIGINT key and its window suffix
-  int kfix = 0;
-  if (!rows->key_serialized && q.key_format == KHIP_FMT_KAFKA && q.ktype[0] != KHIP_TYPE_STRING)
-    kfix = (q.ktype[0] == KHIP_TYPE_INT64 ? 8 : 4) +
-           (q.window_kind == KHIP_WINDOW_SESSION ? 16 : q.window_kind != KHIP_WINDOW_NONE ? 8 : 0);
-  if (n) {
-    KHIP_TRY(s->tsum.ensure((size_t)(2 * (nT + 1)) * 8));
-    int64_t* ts = s->tsum.as<int64_t>();
-    if (s->pb) {
-      KHIP_TRY(s->pb_bad.ensure(8));
-      if (s->has_arr) KHIP_TRY_HIP(hipMemsetAsync(s->pb_bad.p, 0, 8, s->stream));
-      hipLaunchKernelGGL(s->has_arr ? k_sink_measure_pb<true> : k_sink_measure_pb<false>, dim3((unsigned)nT), dim3(256), 0,
-                         s->stream, s->dq.as<SinkParams>(), r, n, kfix, nT, koff, voff, ts, pb_id, s->pb_opt,
-                         s->pb_bad.as<int32_t>());
-    } else if (avro)
-      hipLaunchKernelGGL(s->has_arr ? k_sink_measure_avro<true> : k_sink_measure_avro<false>, dim3((unsigned)nT), dim3(256), 0,
-                         s->stream, s->dq.as<SinkParams>(), r, n, kfix, nT, koff, voff, ts);
-    else
-      hipLaunchKernelGGL(s->has_arr ? k_sink_measure<true> : k_sink_measure<false>, dim3((unsigned)nT), dim3(256), 0, s->stream,
-                         s->dq.as<SinkParams>(), r, n, kfix, nT, koff, voff, ts);
-    KHIP_TRY_HIP(hipGetLastError());
-    int64_t tk = 0, tv = 0;
-    int32_t bad = 0;
-    if (s->pb && s->has_arr) KHIP_TRY_HIP(hipMemcpyAsync(&bad, s->pb_bad.p, 4, hipMemcpyDeviceToHost, s->stream));
-    if (!kfix) KHIP_TRY(sk_scan(s, s->bsum, ts, nT, &tk, false));
-    KHIP_TRY(sk_scan(s, s->bsum2, ts + nT + 1, nT, &tv, true));
-    if (bad)
-      return fail(KHIP_E_UNSUPPORTED, "a NULL array element has no PROTOBUF form (the query stays with the reference)");
-    ktot = kfix ? (int64_t)kfix * n : tk;
-    vtot = tv;
-  } else {
-    const int64_t z = 0;
-    if (dev_out) {
-      KHIP_TRY_HIP(hipMemcpyAsync(koff, &z, 8, hipMemcpyHostToDevice, s->stream));
-      KHIP_TRY_HIP(hipMemcpyAsync(voff, &z, 8, hipMemcpyHostToDevice, s->stream));
-      KHIP_TRY_HIP(hipStreamSynchronize(s->stream));
-    }
-  }
-  out->key_len = ktot;
-  out->value_len = vtot;
-  if (ktot > out->key_capacity || vtot > out->value_capacity) return fail(KHIP_E_BUFFER, "sink output capacity too small");
-  if (n && (ktot && !out->key_bytes)) return fail(KHIP_E_INVALID, "key_bytes");
-  if (n && (vtot && !out->value_bytes)) return fail(KHIP_E_INVALID, "value_bytes");
-  uint8_t *kb = out->key_bytes, *vb = out->value_bytes, *vn = out->value_null;
-  if (!dev_out) {
-    KHIP_TRY(s->kbytes.ensure((size_t)std::max<int64_t>(ktot, 8)));
-    KHIP_TRY(s->vbytes.ensure((size_t)std::max<int64_t>(vtot, 8)));
-    KHIP_TRY(s->vnull.ensure((size_t)std::max<int64_t>(n, 8)));
-    kb = s->kbytes.as<uint8_t>();
-    vb = s->vbytes.as<uint8_t>();
-    vn = s->vnull.as<uint8_t>();
-  }
-  if (n) {
-    const int kwords = kfix && q.ktype[0] == KHIP_TYPE_INT64 && ((uintptr_t)kb & 7) == 0 ? kfix / 8 : 0;
-    if (s->pb)
-      hipLaunchKernelGGL(s->has_arr ? k_sink_write_arr_pb : k_sink_write_pb, dim3((unsigned)nT), dim3(256), 0, s->stream,
-                         s->dq.as<SinkParams>(), r, n, kfix, kwords, nT, s->tsum.as<int64_t>(), koff, kb, voff, vb, vn,
-                         pb_id, s->pb_opt);
-    else if (avro)
-      hipLaunchKernelGGL(s->has_arr ? k_sink_write_arr_avro : k_sink_write_avro, dim3((unsigned)nT), dim3(256), 0, s->stream,
-                         s->dq.as<SinkParams>(), r, n, kfix, kwords, nT, s->tsum.as<int64_t>(), koff, kb, voff, vb, vn,
-                         s->avro_id);
-    else
-      hipLaunchKernelGGL(s->has_arr ? k_sink_write_arr : k_sink_write, dim3((unsigned)nT), dim3(256), 0, s->stream,
-                         s->dq.as<SinkParams>(), r, n, kfix, kwords, nT, s->tsum.as<int64_t>(), koff, kb, voff, vb, vn);
-    KHIP_TRY_HIP(hipGetLastError());
-  }
-  if (!dev_out) {
-    KHIP_TRY_HIP(hipMemcpyAsync(out->key_offsets, koff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s->stream));
-    KHIP_TRY_HIP(hipMemcpyAsync(out->value_offsets, voff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s->stream));
-    if (n) KHIP_TRY_HIP(hipMemcpyAsync(out->value_null, vn, (size_t)n, hipMemcpyDeviceToHost, s->stream));
-    if (ktot) KHIP_TRY_HIP(hipMemcpyAsync(out->key_bytes, kb, (size_t)ktot, hipMemcpyDeviceToHost, s->stream));
-    if (vtot) KHIP_TRY_HIP(hipMemcpyAsync(out->value_bytes, vb, (size_t)vtot, hipMemcpyDeviceToHost, s->stream));
-  }
-  KHIP_TRY_HIP(hipStreamSynchronize(s->stream));
-  return KHIP_OK;
+  KHIP_TRY(enc_stage_rows(s, rows, c));
+  KHIP_TRY(enc_measure(s, rows, out, c));
+  KHIP_TRY(enc_out_buffers(s, out, c));
+  KHIP_TRY(enc_write(s, c));
+  return enc_copy_out(s, out, c);
 }
 
 khip_status khip_sink_sync(khip_sink* s) {

@@ -145,6 +145,48 @@ def test_device_outputs_long_rows(prod, n):
     s.close()
 
 
+@pytest.mark.parametrize("vfmt", ["JSON", "DELIMITED"])
+def test_staged_and_bytewise_waves_in_one_call(prod, vfmt):
+    """One call whose waves (64 rows) take both ways out of k_sink_write: waves of short rows, whose
+    values fit the 2048-byte wave stage, beside waves of long rows, which are written byte by byte,
+    and one wave that is half short and half long (byte-wise).  700 rows: three tiles, the last one
+    partial, each with both kinds of wave.  A short row has one-digit values in all five columns (a
+    JSON row of five one-letter columns is 31 bytes or more, '7.0' for a DOUBLE, so NULLs would only
+    lengthen it); every eighth row is a tombstone, which leaves a short JSON wave 56 x 35 = 1960
+    bytes.  A long row has five columns of large negative BIGINTs and DOUBLEs, over 100 bytes."""
+    n = 700
+    rng = np.random.default_rng(7)
+    kind = {2: "long", 3: "long", 5: "half", 6: "long", 9: "long"}  # per wave; the others are short
+    wave = np.arange(n) // 64
+    long_row = np.array([kind.get(int(w)) == "long" or (kind.get(int(w)) == "half" and i % 64 >= 32)
+                         for i, w in enumerate(wave)])
+    types = ["INT64", "DOUBLE", "INT64", "DOUBLE", "INT64"]
+    cols = []
+    for t in types:
+        small = rng.integers(0, 10, n)
+        if t == "INT64":
+            cols.append(np.where(long_row, rng.integers(-2**63, -2**62, n, dtype=np.int64), small).astype(np.int64))
+        else:
+            cols.append(np.where(long_row, -rng.uniform(1e-300, 1.0, n) * 1e200, small.astype(np.float64)))
+    tomb = (np.arange(n) % 8 == 3).astype(np.uint8)
+    vc = [(nm, t, c) for c, (nm, t) in enumerate(zip("ABCDE", types))]
+    s = abi.SinkHandle(prod, "KAFKA", [("K", "INT64")], vfmt, vc)
+    snap = _rows(n, keys=np.arange(n, dtype=np.int64), values=cols, nulls=[np.zeros(n, bool)] * 5)
+    host = s.encode(snap, tombstone=tomb)
+    assert s.encode(snap, tombstone=tomb, device_out=True, align=5) == host
+    for i in range(n):
+        assert host[0][i] == struct.pack(">q", i)
+        exp = sink_ref.encode_value(vfmt, [(c[0], c[1]) for c in vc],
+                                    [int(cols[c][i]) if types[c] == "INT64" else float(cols[c][i]) for c in range(5)],
+                                    tombstone=bool(tomb[i]))
+        assert host[1][i] == exp, (i, host[1][i], exp)
+    wlen = [sum(len(v) for v in host[1][w:w + 64] if v is not None) for w in range(0, n, 64)]
+    for w, bytes_ in enumerate(wlen):  # the stage holds a wave of at most 2048 bytes
+        assert (bytes_ > 2048) == (w in kind), (w, bytes_)
+        assert bytes_ > 0
+    s.close()
+
+
 @pytest.mark.parametrize("dev_out", [False, True])
 def test_json_column_names_escaped(prod, dev_out):
     """JSON object columns print '{' / ',' + the escaped name + ':' from text built once on the

@@ -6,7 +6,7 @@ OFFSET as the JSON lists the reference writes.
    test_sink_array_ref.py): every element type with L in {1, 3, 8, 29} and a column of L = 100, row
    counts at the tile and wave edges, host and device outputs at several alignments, host and
    device rows.
-2. Tiles whose values fit k_sink_write_arr's stage (abi.SINK_ARRAY_STAGE bytes per round) beside
+2. Tiles whose values fit k_sink_write_arr<TextEnc>'s stage (abi.SINK_ARRAY_STAGE bytes per round) beside
    tiles that take several rounds, with rows across a round's edge.
 3. KHIP_E_BUFFER, 4. the QTT cases end to end (aggregate -> changes -> sink records),
 5. the rejections, 6. scalar sinks after an array sink.

@@ -3,8 +3,8 @@
 
 One process, device rows to device record bytes (khip_sink_encode), sink_json's key (a KAFKA BIGINT
 key and the 8-byte TUMBLING window start) and its row count (22M by default):
-    scalar          {"KSQL_COL_0":n}             the yardstick: sink_json's own value, k_sink_write
-    arr1 / 3 / 8    {"KSQL_COL_0":[n,...]}       BIGINT lists of L = 1, 3 and 8, all full, k_sink_write_arr
+    scalar          {"KSQL_COL_0":n}             the yardstick: sink_json's own value, k_sink_write<TextEnc>
+    arr1 / 3 / 8    {"KSQL_COL_0":[n,...]}       BIGINT lists of L = 1, 3 and 8, all full, k_sink_write_arr<TextEnc>
 Every element is drawn as sink_json draws its count (1..30), so a list's bytes differ from the
 scalar's by the brackets, the commas and the further elements only.  The handles are alternated
 step by step; a step is one khip_sink_encode, which returns after the device has finished.  Prints

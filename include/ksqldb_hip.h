@@ -936,6 +936,129 @@ khip_status khip_serde_create(const khip_serde_desc* desc, khip_serde** out);
 khip_status khip_serde_decode(khip_serde* s, const khip_raw_batch* in, khip_batch* out, int64_t* n_errors);
 khip_status khip_serde_destroy(khip_serde* s);
 
+/* ------------------------------- WHERE filters and computed columns (between decode and push) */
+
+/* The StreamFilter (WHERE, S/StreamFilterBuilder.java:44-69 over X/transform/sqlpredicate/
+ * SqlPredicate.java:75-101) and the StreamSelect in front of an aggregate ("Aggregate/Prepare",
+ * S/StreamSelectBuilder.java:40-118 over X/transform/select/SelectValueMapper.java:104-132), for the
+ * closed set of expressions the column types of this path can express: INT / BIGINT / DOUBLE
+ * arithmetic, comparisons, boolean logic, null tests and numeric casts.  STRING / DECIMAL / temporal
+ * values, functions, CASE, LIKE, IN, subscripts and lambdas stay with the CPU builder.
+ *
+ * A program is a postfix sequence of int64 words over a typed operand stack, checked and typed once
+ * at create.  One instruction is one word: the opcode in the low 8 bits, KHIP_X_COL's column index
+ * in bits 32 and up.  A constant instruction is followed by one word holding the value: an int32
+ * sign-extended, an int64, or the raw bits of a double.  Value types are KHIP_TYPE_INT32 / INT64 /
+ * DOUBLE, plus a BOOLEAN that never leaves the program.
+ *
+ * Every value is VALUE, NULL or ERROR (ERROR: the reference's generated Java threw; X/codegen/
+ * SqlToJavaVisitor.java:587-622, :677-692, :812-981, helpers/CastEvaluator.java:69-88, :201-209,
+ * CompiledExpression.java:81-97):
+ *   COL         VALUE or NULL by the column's validity bit.  Constants are VALUE.
+ *   ADD SUB MUL DIV MOD NEG
+ *               Java binary numeric promotion (INT op INT = INT; with a BIGINT, BIGINT; with a
+ *               DOUBLE, DOUBLE).  A NULL operand gives ERROR (the unboxing NullPointerException), and
+ *               so does an integer DIV / MOD by zero (ArithmeticException).  int / long arithmetic
+ *               wraps, division truncates toward zero, MIN / -1 = MIN, x % -1 = 0.  DOUBLE + - * /
+ *               are single correctly rounded IEEE operations (a * b + c is never fused), MOD is C
+ *               fmod, x / 0.0 is +-Infinity or NaN.
+ *   CAST_I32 CAST_I64 CAST_F64
+ *               null-safe (NULL stays NULL, ERROR stays ERROR).  long -> int keeps the low 32 bits;
+ *               int / long -> double rounds to nearest even; double -> int / long saturates, NaN -> 0.
+ *   EQ NE LT LE GT GE
+ *               two numeric operands, promoted; BOOLEAN.  Left ERROR -> ERROR; left NULL -> false
+ *               without evaluating the right side (its ERROR is lost); then right ERROR -> ERROR,
+ *               right NULL -> false.  EQ is (a <= b) && (a >= b), NE is (a < b) || (a > b): both
+ *               false with a NaN operand; -0.0 EQ 0.0.
+ *   DISTINCT    IS DISTINCT FROM: both sides are always evaluated, so either ERROR propagates; with
+ *               a NULL side the result is (left is NULL) XOR (right is NULL); otherwise NE.
+ *   AND OR NOT  over BOOLEAN, short-circuit like && and ||: A AND B is ERROR when A is, or when A is
+ *               true and B is ERROR; A OR B when A is ERROR, or A is false and B is ERROR.  NOT keeps
+ *               ERROR.  A BOOLEAN is never NULL.
+ *   IS_NULL IS_NOT_NULL
+ *               of a numeric value, or of a bare COL of a KHIP_TYPE_STRING column (the only use of
+ *               one: the decoder carries its validity alone).  An ERROR operand gives ERROR.
+ * Sinks pop one value each:
+ *   WHERE       BOOLEAN; at most one, and the program's first sink.  A row is kept when the value is
+ *               true; ERROR counts as false (SqlPredicate.java:95-96).
+ *   OUT         numeric: the next output value column, in order.  NULL and ERROR both clear the
+ *               validity bit (SelectValueMapper.java:131); the element is then 0.
+ *   KEY         INT32 / INT64, at most one: the computed GROUP BY key (S/GroupByParamsFactory.java:
+ *               137-150, :92-100) — the output's key_i64, widened; NULL / ERROR clear key_valid.
+ * BETWEEN, NOT BETWEEN, IS NOT DISTINCT FROM and unary plus are lowered by the caller.
+ *
+ * KHIP_E_UNSUPPORTED at create: more than 64 words, a stack deeper than 8, more than 32 OUT columns
+ * (implied by the word limit today: an OUT takes at least two words, so 64 words hold at most 32),
+ * more than 64 input columns.  KHIP_E_INVALID: an unknown opcode, a column index out of range, stack
+ * underflow or values left at the end, a type error, a second or late WHERE, a second KEY, a
+ * truncated constant, an empty program. */
+#define KHIP_X_COL 1        /* push column (word >> 32)                         */
+#define KHIP_X_CONST_I32 2  /* push the next word as an INT                     */
+#define KHIP_X_CONST_I64 3  /* ... as a BIGINT                                  */
+#define KHIP_X_CONST_F64 4  /* ... as the bits of a DOUBLE                      */
+#define KHIP_X_ADD 10
+#define KHIP_X_SUB 11
+#define KHIP_X_MUL 12
+#define KHIP_X_DIV 13
+#define KHIP_X_MOD 14
+#define KHIP_X_NEG 15
+#define KHIP_X_CAST_I32 20
+#define KHIP_X_CAST_I64 21
+#define KHIP_X_CAST_F64 22
+#define KHIP_X_EQ 30
+#define KHIP_X_NE 31
+#define KHIP_X_LT 32
+#define KHIP_X_LE 33
+#define KHIP_X_GT 34
+#define KHIP_X_GE 35
+#define KHIP_X_DISTINCT 36
+#define KHIP_X_AND 40
+#define KHIP_X_OR 41
+#define KHIP_X_NOT 42
+#define KHIP_X_IS_NULL 50
+#define KHIP_X_IS_NOT_NULL 51
+#define KHIP_X_WHERE 60
+#define KHIP_X_OUT 61
+#define KHIP_X_KEY 62
+
+typedef struct khip_expr khip_expr;
+
+/* col_types: the n_cols input columns' KHIP_TYPE_* (INT32 / INT64 / DOUBLE / STRING). */
+khip_status khip_expr_create(int32_t device, int32_t n_cols, const int32_t* col_types,
+                             const int64_t* code, int32_t n_code, khip_expr** out);
+/* The OUT columns and their KHIP_TYPE_*, as typed at create. */
+khip_status khip_expr_n_out(const khip_expr* e, int32_t* n_out);
+khip_status khip_expr_out_type(const khip_expr* e, int32_t i, int32_t* out_type);
+
+/* Run the program over a batch.  `in` is a KHIP_MEM_HOST or KHIP_MEM_DEVICE batch whose n_cols
+ * covers every column the program names; a column's elements are 4 bytes for INT32 and 8 for every
+ * other type (a STRING column as khip_serde_decode writes it: only its validity is read).  *out
+ * becomes a KHIP_MEM_DEVICE batch owned by the handle, valid until the handle's next apply or its
+ * destroy:
+ *   - with a WHERE, the kept rows in arrival order.  A row whose row_valid bit is 0 (a null value)
+ *     is dropped by a WHERE; without one every row passes, null-value rows keep row_valid 0 and get
+ *     NULL outputs.  Rows with a null key or ts < 0 are rows like any other: the aggregate drops and
+ *     counts them;
+ *   - the key (key_i64; or key_offsets / key_bytes, offsets rebuilt from 0; or the KEY sink's
+ *     value), key_valid, row_valid, ts, and partition / stream_time when the input has them;
+ *   - n_cols = the OUT columns, with col_data and col_valid for each.
+ * A NULL input bitmap means all valid.  Without a WHERE the arrays that pass through untouched (ts,
+ * keys, key_valid, row_valid, partition, stream_time) are the input's own for a device input — keep
+ * it alive while *out is used — and may be NULL where the input's were; with a WHERE every bitmap
+ * is written.  *n_errors (may be NULL) receives the (row, sink) evaluations that ended in ERROR (the
+ * processing log's records): the WHERE of every non-null row, OUT and KEY of the kept rows.
+ * The handle owns a blocking stream: a device input produced on the default stream needs no extra
+ * sync.  The call returns after the device has finished, like khip_serde_decode (a WHERE needs the
+ * row count on the host anyway): *out can go straight to khip_agg_push or any other handle, whose
+ * stream does not order against this one, and a host input's arrays may be reused at once.
+ * khip_expr_sync waits for the handle's stream and is kept for symmetry with the other handles.
+ * n_rows = 0, and a WHERE that keeps nothing, are valid.
+ * Under KHIP_TIME_SUPPLIED the stream-time scan (khip_stream_time_scan) belongs AFTER this step:
+ * filtered rows never reach the aggregate and do not advance stream time. */
+khip_status khip_expr_apply(khip_expr* e, const khip_batch* in, khip_batch* out, int64_t* n_errors);
+khip_status khip_expr_sync(khip_expr* e);
+khip_status khip_expr_destroy(khip_expr* e);
+
 /* ---------------------------------------------- serialization (device columns → record bytes) */
 
 /* The output side of GenericKeySerDe / GenericRowSerDe for a sink topic (ksqldb-serde/src/main/

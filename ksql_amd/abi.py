@@ -277,6 +277,12 @@ PRODUCT_ONLY = {
     "sink_set_schema_id": ([_P, i32]),
     "sink_sync": ([_P]),
     "sink_destroy": ([_P]),
+    "expr_create": ([i32, i32, C.POINTER(i32), C.POINTER(i64), i32, C.POINTER(_P)]),
+    "expr_n_out": ([_P, C.POINTER(i32)]),
+    "expr_out_type": ([_P, i32, C.POINTER(i32)]),
+    "expr_apply": ([_P, C.POINTER(Batch), C.POINTER(Batch), C.POINTER(i64)]),
+    "expr_sync": ([_P]),
+    "expr_destroy": ([_P]),
 }
 
 
@@ -1354,6 +1360,168 @@ class SinkHandle:
     def close(self):
         if self.h:
             self.lib.sink_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ------------------------------------------------------------------ WHERE filters / computed columns
+
+# KHIP_X_* opcodes (include/ksqldb_hip.h, "WHERE filters and computed columns")
+X = {"COL": 1, "CONST_I32": 2, "CONST_I64": 3, "CONST_F64": 4,
+     "ADD": 10, "SUB": 11, "MUL": 12, "DIV": 13, "MOD": 14, "NEG": 15,
+     "CAST_I32": 20, "CAST_I64": 21, "CAST_F64": 22,
+     "EQ": 30, "NE": 31, "LT": 32, "LE": 33, "GT": 34, "GE": 35, "DISTINCT": 36,
+     "AND": 40, "OR": 41, "NOT": 42, "IS_NULL": 50, "IS_NOT_NULL": 51,
+     "WHERE": 60, "OUT": 61, "KEY": 62}
+X_CONST = {"I32": "CONST_I32", "I64": "CONST_I64", "F64": "CONST_F64"}
+EXPR_BLOCK = 256  # rows per block of the expression kernels (csrc/khip_expr.hip XB)
+EXPR_MAX_CODE, EXPR_MAX_STACK, EXPR_MAX_OUT, EXPR_MAX_COLS = 64, 8, 32, 64
+
+
+def _i64(v):
+    """Python int → the signed 64-bit word holding its low 64 bits."""
+    v &= (1 << 64) - 1
+    return v - (1 << 64) if v >> 63 else v
+
+
+def expr_words(*trees):
+    """Nested tuples → the postfix word list of khip_expr_create.  A tree is ("COL", c),
+    ("I32" | "I64" | "F64", value), or (OP, operand...) with OP a key of X; the sinks are trees too:
+    ("WHERE", t), ("OUT", t), ("KEY", t).  Several trees are one program, in order:
+    expr_words(("WHERE", ("GT", ("MUL", ("COL", 0), ("COL", 1)), ("I64", 100))), ("OUT", ("COL", 0)))."""
+    words = []
+
+    def walk(t):
+        op = t[0]
+        if op == "COL":
+            words.append(X["COL"] | (int(t[1]) << 32))
+        elif op in X_CONST:
+            words.append(X[X_CONST[op]])
+            if op == "F64":
+                words.append(int(np.array([t[1]], np.float64).view(np.int64)[0]))
+            else:
+                v = int(t[1])
+                if op == "I32":  # an int32, sign-extended
+                    v &= 0xFFFFFFFF
+                    v -= (v >> 31) << 32
+                words.append(_i64(v))
+        else:
+            for sub in t[1:]:
+                walk(sub)
+            words.append(X[op])
+    for t in trees:
+        walk(t)
+    return words
+
+
+def expr_trees(words):
+    """The inverse of expr_words for a well-formed program: the list of sink trees."""
+    names = {v: k for k, v in X.items()}
+    arity = dict({k: 2 for k in ("ADD", "SUB", "MUL", "DIV", "MOD", "EQ", "NE", "LT", "LE", "GT", "GE", "DISTINCT",
+                                 "AND", "OR")},
+                 **{k: 1 for k in ("NEG", "CAST_I32", "CAST_I64", "CAST_F64", "NOT", "IS_NULL", "IS_NOT_NULL", "WHERE",
+                                   "OUT", "KEY")})
+    stack, out, i = [], [], 0
+    while i < len(words):
+        w = words[i]
+        name = names[w & 0xFF]
+        i += 1
+        if name == "COL":
+            stack.append(("COL", w >> 32))
+        elif name.startswith("CONST_"):
+            k = words[i]
+            i += 1
+            stack.append(("F64", float(np.array([k], np.int64).view(np.float64)[0])) if name == "CONST_F64"
+                         else (name[len("CONST_"):], int(k)))
+        else:
+            n = arity[name]
+            args = stack[len(stack) - n:]
+            del stack[len(stack) - n:]
+            node = (name, *args)
+            (out if name in ("WHERE", "OUT", "KEY") else stack).append(node)
+    assert not stack, stack
+    return out
+
+
+class _Applied:
+    """An applied batch: the khip_batch struct, and the input it may point into, kept alive."""
+
+    def __init__(self, struct, keep):
+        self.struct = struct
+        self._keep = keep
+
+
+class Expr:
+    """khip_expr_*: a WHERE filter and computed columns / GROUP BY key over a batch, on the device."""
+
+    def __init__(self, lib, col_types, words, device=0):
+        """col_types: INT32 / INT64 / DOUBLE / STRING per input column; words: expr_words(...)."""
+        self.lib = lib
+        tmap = dict(TYPE, STRING=TYPE_STRING)
+        ct = [tmap[t] if isinstance(t, str) else t for t in col_types]
+        self._ct = (i32 * max(len(ct), 1))(*ct)
+        self._code = (i64 * max(len(words), 1))(*words)
+        self.h = C.c_void_p()
+        lib.check(lib.expr_create(device, len(ct), self._ct, self._code, len(words), C.byref(self.h)), "expr_create")
+        n = i32()
+        lib.check(lib.expr_n_out(self.h, C.byref(n)), "expr_n_out")
+        self.out_types = []
+        for c in range(n.value):
+            t = i32()
+            lib.check(lib.expr_out_type(self.h, c, C.byref(t)), "expr_out_type")
+            self.out_types.append(t.value)
+
+    def apply(self, batch, count_errors=True):
+        """batch: a HostBatch / DeviceBatch / decoded batch.  Returns (device batch object usable by
+        AggHandle.push at once, valid until the next apply; n_errors or None).  The input is kept alive with it."""
+        out = Batch()
+        nerr = i64(-1)
+        self.lib.check(self.lib.expr_apply(self.h, C.byref(batch.struct), C.byref(out),
+                                           C.byref(nerr) if count_errors else None), "expr_apply")
+        return _Applied(out, batch), (nerr.value if count_errors else None)
+
+    def columns(self, applied):
+        """Copy an applied batch back to the host (tests): dict of numpy arrays; bitmaps as bool arrays
+        (None where the batch has no such array)."""
+        self.sync()
+        b = applied.struct
+        n = b.n_rows
+        nb = (n + 7) // 8
+
+        def dget(ptr, count, dtype):
+            if not ptr:
+                return None
+            a = np.zeros(max(count, 1), dtype)
+            if count:
+                _hip_copy(a, ptr, a.nbytes)
+            return a[:count]
+
+        def bits(ptr):
+            a = dget(ptr, nb, np.uint8)
+            return None if a is None else np.unpackbits(a, bitorder="little")[:n].astype(bool)
+        res = {"n": n, "ts": dget(b.ts, n, np.int64), "key": dget(b.key_i64, n, np.int64),
+               "key_valid": bits(b.key_valid), "row_valid": bits(b.row_valid),
+               "partition": dget(b.partition, n, np.int32), "stream_time": dget(b.stream_time, n, np.int64),
+               "key_offsets": dget(b.key_offsets, n + 1, np.int64), "key_bytes": None}
+        if res["key_offsets"] is not None:
+            res["key_bytes"] = dget(b.key_bytes, int(res["key_offsets"][n]), np.uint8)
+            if res["key_bytes"] is None:
+                res["key_bytes"] = np.zeros(0, np.uint8)
+        res["cols"] = [dget(b.col_data[c], n, NP_TYPE[t]) for c, t in enumerate(self.out_types)]
+        res["valid"] = [bits(b.col_valid[c]) for c in range(len(self.out_types))]
+        return res
+
+    def sync(self):
+        self.lib.check(self.lib.expr_sync(self.h), "expr_sync")
+
+    def close(self):
+        if self.h:
+            self.lib.expr_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
